@@ -15,7 +15,17 @@ GPU it checks that N devices exist (exit 2 otherwise, never a silent 1-GPU run),
 ranks of this script (one per GPU, rendezvous on 127.0.0.1) and relays rank 0's JSON line.  Under
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` it is a rank directly.
 
-The same line carries the op-pipeline half of the metric ("GB/s vs HBM roofline"):
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the result line
+(`value`, `ms_per_step`, the train step's own record and its `train_roofline`, priced from the timed steps alone).
+--dump-outputs DIR also writes what the last timed step handed its caller, as DIR/<name>.npy (float32): `loss`, and a
+fixed, seeded sample of the model it updated -- `params` after Adam, the step's all-reduced `grads`, the batch-norm
+running statistics `bn_stats` (step_outputs()).  Inputs and weights are seeded, and the train legs run on torch's
+deterministic implementations: the same arguments give the same inputs and the same outputs.
+
+Everything else runs with --full only (--quick, --no-cpu-baseline, --no-128 and --no-train trim it): the teacher-forced
+step and the alternation after the headline region, the all-reduce timed on its own (N > 1), the train step at 128x128,
+the conv kernel table behind `roofline`, the CPU baselines with the parity gate, and the op-pipeline half of the metric
+("GB/s vs HBM roofline"):
   executor.cfg2_bs64     BASELINE configs[1]: 6-op executor sequence fwd + L1 + bwd, bs=64 256x256
   executor.bs256         the same at bs=256 (the north-star >= 60 % target size)
   executor.cfg5_16x512   configs[4] per-GPU shape: 16 x 512x512, ops [5,3,5,3,0,1,2,6]
@@ -24,6 +34,8 @@ timings.  `roofline` = the dominant hand-written kernel of the cfg2 fused step (
 `train_roofline` = the train step against the fp32 matrix peak (4.34 TFLOP per bs=64 step).
 `cpu_baseline` = the oracle (oracle/cpu_ref.py) on this node's host cores for configs[0], [1]
 and (bounded sample) [2], N=1 only.
+
+    python bench.py --gpus N --steps K --warmup W --full
 """
 import argparse
 import ctypes
@@ -657,9 +669,48 @@ def synthetic_requests(B, g):
     return x
 
 
-def train_step_bench(ctx, B, H, W, steps, warmup, with_extras=True):
+DUMP_PER_TENSOR = 8192          # elements sampled per parameter tensor by step_outputs (smaller tensors go in whole)
+DUMP_SEED = 20240
+
+
+def step_outputs(model, trainer, loss):
+    """What one train step hands its caller: the loss it returns and the model it updated in place -- the parameters after
+    Adam, the step's (all-reduced) gradients, the batch-norm running statistics.  Of every parameter tensor a fixed, seeded
+    sample of DUMP_PER_TENSOR elements in the tensor's logical order (all of it when smaller), concatenated in the trainer's
+    parameter order: 415 k of the actor's 22 M parameters.  float32 numpy arrays by name."""
+    import numpy as np
+    import torch
+    params = trainer.grads.params
+    with torch.no_grad():
+        pv, gv = [], []
+        for i, p in enumerate(params):
+            n = p.numel()
+            if n <= DUMP_PER_TENSOR:
+                idx = torch.arange(n)
+            else:
+                idx = torch.from_numpy(np.sort(np.random.default_rng([DUMP_SEED, i]).choice(n, DUMP_PER_TENSOR, replace=False)))
+            idx = idx.to(p.device)
+            pv.append(p.detach().reshape(-1)[idx])
+            gv.append(p.grad.reshape(-1)[idx])
+        bn = [b.detach().reshape(-1).float() for name, b in model.named_buffers() if 'running_' in name]
+        out = {'loss': loss.detach().float().reshape(1), 'params': torch.cat(pv), 'grads': torch.cat(gv),
+               'bn_stats': torch.cat(bn) if bn else torch.zeros(0)}
+        return {k: v.cpu().numpy().astype(np.float32) for k, v in out.items()}
+
+
+def write_outputs(path, outputs):
+    """--dump-outputs: DIR/<name>.npy for every array of step_outputs()."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, name + '.npy'), arr)
+
+
+def train_step_bench(ctx, B, H, W, steps, warmup, with_extras=True, outputs=None):
     """BASELINE.json configs[2]/[3]: the episode/L1 train step of train_seq2seqL1.py:74-88, FiveK-shaped
-    synthetic batch, random-init weights, fp32; exactly `steps` timed steps."""
+    synthetic batch, random-init weights, fp32; exactly `steps` timed steps.  with_extras: also the all-reduce on its
+    own (N > 1), the teacher-forced step and the alternation, after the timed region.  outputs: a dict that receives
+    step_outputs() of the last timed step."""
     import torch
     import t2onet_amd
     from t2onet_amd.actor import Actor
@@ -698,11 +749,14 @@ def train_step_bench(ctx, B, H, W, steps, warmup, with_extras=True):
     dt_local = time.perf_counter() - t0
     dt = ctx['max_over_ranks'](dt_local)
     spread = {'min': round(dt_local / steps * 1e3, 3), 'max': round(dt_local / steps * 1e3, 3)}
+    if outputs is not None:                                # before anything below touches the gradients or the weights
+        outputs.update(step_outputs(model, tr, loss))
     allreduce_ms = None
     if dist is not None:
         t = torch.tensor([dt_local, -dt_local], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         spread = {'min': round(-float(t[1]) / steps * 1e3, 3), 'max': round(float(t[0]) / steps * 1e3, 3)}
+    if dist is not None and with_extras:
         # the step's one collective on its own: HIP events around the flat-buffer all-reduce (RCCL) on this rank
         evs = []
         for _ in range(5):
@@ -972,12 +1026,13 @@ def compact_line(detail, detail_path=None):
     out['config'] = {k: _short(v, 200) for k, v in cfg.items()}
     if 'error' in detail:
         out['error'] = _short(detail['error'], 300)
-    rf = detail.get('roofline') or {}
-    out['roofline'] = rf if 'error' in rf else _pick(rf, (
-        'bound', 'kernel', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'avg_launch_ms', 'launches_per_step',
-        'executed_flop_per_launch', 'credited_frac'))
-    if 'of' in rf:
-        out['roofline']['of'] = _short(rf['of'], 120)
+    rf = detail.get('roofline')
+    if rf:                                  # (--full only: the conv kernel table)
+        out['roofline'] = rf if 'error' in rf else _pick(rf, (
+            'bound', 'kernel', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'avg_launch_ms', 'launches_per_step',
+            'executed_flop_per_launch', 'credited_frac'))
+        if 'of' in rf:
+            out['roofline']['of'] = _short(rf['of'], 120)
     er = detail.get('executor_roofline')
     if er:
         out['executor_roofline'] = _pick(er, ('bound', 'kernel', 'of', 'achieved', 'peak', 'unit', 'frac', 'traffic',
@@ -1199,34 +1254,35 @@ def worker(args):
                         'parallelism': 'dp%d: batch shards, one flat fp32 gradient all-reduce (22.2 M floats) per step' % world},
                        **backend_info),
     }
-    executor = {}
-    try:
-        executor['cfg2_bs64'] = executor_leg(ctx, CFG2_OPS, B, H, W, args.exec_steps, args.exec_warmup, with_api=(world == 1))
-        if not args.quick:
-            executor['bs256'] = executor_leg(ctx, CFG2_OPS, 4 * B, H, W, max(args.exec_steps // 4, 10), max(args.exec_warmup // 2, 3))
-            executor['cfg5_16x512'] = executor_leg(ctx, CFG5_OPS, max(B // 4, 1), 2 * H, 2 * W, args.exec_steps, args.exec_warmup)
-        executor['cfg2_generic'] = executor_leg(ctx, CFG2_GENERIC_OPS, B, H, W, args.exec_steps, args.exec_warmup)
-        fk = executor['cfg2_bs64']['fused']['kernels']
-        dom = max(fk, key=lambda n: fk[n]['ms'])
-        line['executor_roofline'] = {
-            'bound': 'hbm', 'kernel': dom, 'of': 'executor.cfg2_bs64.fused', 'achieved': fk[dom]['hbm_min_GBps'], 'peak': HBM_PEAK_GBS,
-            'unit': 'GB/s', 'frac': round(fk[dom]['hbm_min_GBps'] / HBM_PEAK_GBS, 4), 'traffic': pmc_traffic(dom, P),
-            'moved_bytes_per_launch': hbm_min_bytes(dom, P), 'avg_launch_ms': fk[dom]['ms'],
-            'credited_bytes_per_launch': algorithmic_bytes(dom, P), 'credited_achieved': fk[dom]['GBps'],
-            'credited_frac': round(fk[dom]['GBps'] / HBM_PEAK_GBS, 4),
-            'note': 'dominant hand-written kernel of the op pipeline.  frac = bytes the launch MOVES (read image + gradient, '
-                    'write gradient: 36 B/pixel whatever the fusion) / time / 8 TB/s -- a physical fraction, <= 1.  credited_* '
-                    'uses SURVEY 8(d)\'s materialised accounting (36 B/pixel per operator application the fused launch '
-                    'performs) and may exceed 1.  traffic = PMC bytes when profiles/pmc_traffic.json was measured on this '
-                    'very library, else null'}
-    except Exception as e:                     # noqa: BLE001
-        executor['error'] = '%s: %s' % (type(e).__name__, e)
-    line['executor'] = executor
-    try:                                   # the train step's dominant kernel on its own, HIP-event timed: the line's `roofline`
-        line['conv_kernels'], line['roofline'] = conv_kernel_table(B, H, W, device)
-        line['roofline']['traffic'] = pmc_launch_traffic('k_wino_fused<0>' if line['roofline'].get('kernel') == 'k_wino_fused' else 'k_conv3x3_fwd<2, 1>')
-    except Exception as e:                 # noqa: BLE001
-        line['roofline'] = {'error': '%s: %s' % (type(e).__name__, e)}
+    if args.full:                              # everything beyond the headline, before it (as it always ran)
+        executor = {}
+        try:
+            executor['cfg2_bs64'] = executor_leg(ctx, CFG2_OPS, B, H, W, args.exec_steps, args.exec_warmup, with_api=(world == 1))
+            if not args.quick:
+                executor['bs256'] = executor_leg(ctx, CFG2_OPS, 4 * B, H, W, max(args.exec_steps // 4, 10), max(args.exec_warmup // 2, 3))
+                executor['cfg5_16x512'] = executor_leg(ctx, CFG5_OPS, max(B // 4, 1), 2 * H, 2 * W, args.exec_steps, args.exec_warmup)
+            executor['cfg2_generic'] = executor_leg(ctx, CFG2_GENERIC_OPS, B, H, W, args.exec_steps, args.exec_warmup)
+            fk = executor['cfg2_bs64']['fused']['kernels']
+            dom = max(fk, key=lambda n: fk[n]['ms'])
+            line['executor_roofline'] = {
+                'bound': 'hbm', 'kernel': dom, 'of': 'executor.cfg2_bs64.fused', 'achieved': fk[dom]['hbm_min_GBps'], 'peak': HBM_PEAK_GBS,
+                'unit': 'GB/s', 'frac': round(fk[dom]['hbm_min_GBps'] / HBM_PEAK_GBS, 4), 'traffic': pmc_traffic(dom, P),
+                'moved_bytes_per_launch': hbm_min_bytes(dom, P), 'avg_launch_ms': fk[dom]['ms'],
+                'credited_bytes_per_launch': algorithmic_bytes(dom, P), 'credited_achieved': fk[dom]['GBps'],
+                'credited_frac': round(fk[dom]['GBps'] / HBM_PEAK_GBS, 4),
+                'note': 'dominant hand-written kernel of the op pipeline.  frac = bytes the launch MOVES (read image + gradient, '
+                        'write gradient: 36 B/pixel whatever the fusion) / time / 8 TB/s -- a physical fraction, <= 1.  credited_* '
+                        'uses SURVEY 8(d)\'s materialised accounting (36 B/pixel per operator application the fused launch '
+                        'performs) and may exceed 1.  traffic = PMC bytes when profiles/pmc_traffic.json was measured on this '
+                        'very library, else null'}
+        except Exception as e:                     # noqa: BLE001
+            executor['error'] = '%s: %s' % (type(e).__name__, e)
+        line['executor'] = executor
+        try:                                   # the train step's dominant kernel on its own, HIP-event timed: the line's `roofline`
+            line['conv_kernels'], line['roofline'] = conv_kernel_table(B, H, W, device)
+            line['roofline']['traffic'] = pmc_launch_traffic('k_wino_fused<0>' if line['roofline'].get('kernel') == 'k_wino_fused' else 'k_conv3x3_fwd<2, 1>')
+        except Exception as e:                 # noqa: BLE001
+            line['roofline'] = {'error': '%s: %s' % (type(e).__name__, e)}
     rc = [0]
     if args.no_train:
         line['error'] = '--no-train: executor legs only, no headline value'
@@ -1251,8 +1307,18 @@ def worker(args):
     watchdog = threading.Timer(args.train_timeout, on_timeout)
     watchdog.daemon = True
     watchdog.start()
+    outputs = {} if args.dump_outputs and rank == 0 else None     # (replicas: rank 0's model is every rank's)
+    # the train legs run on the framework's deterministic implementations, so that the same arguments give the same outputs
+    # (--dump-outputs): the step's one framework op that adds atomically on the GPU -- index_add_ into the decoder embedding's
+    # weight gradient, whose rows share operator tokens -- then sums in sorted order.  warn_only: an op without such an
+    # implementation warns instead of failing the run.  New allocations are not NaN-filled (the mode's default): that would
+    # add work to the timed steps.
+    import torch.utils.deterministic
+    nan_fill = torch.utils.deterministic.fill_uninitialized_memory
+    torch.utils.deterministic.fill_uninitialized_memory = False
+    torch.use_deterministic_algorithms(True, warn_only=True)
     try:
-        train = train_step_bench(ctx, B, H, W, args.steps, args.warmup)
+        train = train_step_bench(ctx, B, H, W, args.steps, args.warmup, with_extras=args.full, outputs=outputs)
         line['value'] = train['images_per_sec']
         line['ms_per_step'] = train['ms_per_step']
         line['train_step'] = train
@@ -1263,9 +1329,11 @@ def worker(args):
         line['error'] = 'train step: %s: %s' % (type(e).__name__, e)
         rc[0] = 1
     watchdog.cancel()
+    if rc[0] == 0 and outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     # EXTRA key (the headline stays configs[2]): the same step at the size the reference itself trains at -- 128 x 128 crops,
     # bs = 64 (README.md:91, datasets/FiveKdataset.py:25,68).  A quarter of the pixels: the encoder's maps are 32 x 32 ... 4 x 4.
-    if rc[0] == 0 and not args.quick and not args.no_128 and (H, W) == (256, 256) and world == 1:
+    if rc[0] == 0 and args.full and not args.quick and not args.no_128 and (H, W) == (256, 256) and world == 1:
         try:
             torch.cuda.empty_cache()
             t128 = train_step_bench(ctx, B, 128, 128, args.steps, max(args.warmup, 3), with_extras=False)
@@ -1276,10 +1344,12 @@ def worker(args):
                                           by_kernel_family=t128['roofline']['by_kernel_family'])
         except Exception as e:             # noqa: BLE001
             line['train_step_128'] = {'error': '%s: %s' % (type(e).__name__, e)}
+    torch.use_deterministic_algorithms(False)
+    torch.utils.deterministic.fill_uninitialized_memory = nan_fill
     # the CPU baseline LAST (reported, never the target): run before the train leg, its eager CPU autograd over 64 images left
     # the process in a state in which the supervised / episode alternation read 100-113 ms per pair instead of 83 (the headline
     # and each step on its own were unaffected; not the intra-op thread count -- pinned to 1, the same)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             line['cpu_baseline'] = cpu_baselines(H, W, args.cpu_sample, args.cpu_train_sample)
             if line.get('value') and line['cpu_baseline'].get('value'):     # (vs_baseline stays null: BASELINE.md publishes no number)
@@ -1300,21 +1370,28 @@ def main():
     ap.add_argument('--warmup', type=int, default=5, help='untimed train steps (the first also captures the encoder hipGraphs)')
     ap.add_argument('--batch', type=int, default=64, help='images per GPU')
     ap.add_argument('--size', type=int, default=256)
-    ap.add_argument('--exec-steps', type=int, default=200, help='timed steps of each executor leg')
-    ap.add_argument('--exec-warmup', type=int, default=20)
-    ap.add_argument('--quick', action='store_true', help='skip the bs=256 and cfg5 executor legs')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-128', action='store_true', help='skip the extra train_step_128 leg (profiling passes: its shorter launches of the same kernels would mix into the per-kernel averages)')
+    ap.add_argument('--exec-steps', type=int, default=200, help='with --full: timed steps of each executor leg')
+    ap.add_argument('--exec-warmup', type=int, default=20, help='with --full: untimed steps of each executor leg')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beyond the headline: executor legs, conv kernel table (`roofline`), teacher-forced step '
+                         'and alternation, all-reduce on its own (N > 1), the 128x128 train step, CPU baselines and parity')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed train step computed to DIR/<name>.npy (float32; see step_outputs)')
+    ap.add_argument('--quick', action='store_true', help='with --full: skip the bs=256 and cfg5 executor legs and the 128x128 step')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-128', action='store_true', help='with --full: skip the extra train_step_128 leg (profiling passes: its shorter launches of the same kernels would mix into the per-kernel averages)')
     ap.add_argument('--no-train', action='store_true',
-                    help='executor legs only (profiling passes; the line then has no headline value)')
-    ap.add_argument('--cpu-sample', type=int, default=64, help='images of the configs[1] CPU baseline')
-    ap.add_argument('--cpu-train-sample', type=int, default=64, help='images of the configs[2] CPU baseline (the headline\'s own batch; 1 warm-up + 3 reps, ~35 s on the MI355X host)')
+                    help='with --full: executor legs only (profiling passes; the line then has no headline value)')
+    ap.add_argument('--cpu-sample', type=int, default=64, help='with --full: images of the configs[1] CPU baseline')
+    ap.add_argument('--cpu-train-sample', type=int, default=64, help='with --full: images of the configs[2] CPU baseline (the headline\'s own batch; 1 warm-up + 3 reps, ~35 s on the MI355X host)')
     ap.add_argument('--train-timeout', type=int, default=600, help='seconds before the train-step leg is abandoned')
     ap.add_argument('--launch-timeout', type=int, default=1500, help='launcher: seconds before the ranks are stopped')
     ap.add_argument('--cpu-probe', default=None, help=argparse.SUPPRESS)
     ap.add_argument('--selftest', action='store_true',
                     help='CPU/gloo stand-in step through the launcher, rendezvous and timing code (tests only)')
     args = ap.parse_args()
+    if args.no_train and not args.full:
+        ap.error('--no-train keeps only the --full legs: give --full with it')
     if args.cpu_probe:
         return cpu_probe_main(args.cpu_probe)
     if args.gpus < 1:

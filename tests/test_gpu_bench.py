@@ -23,7 +23,7 @@ def _free_port():
 def test_one_rank_job_with_the_c_abi_allreduce_on_the_timed_path(tmp_path):
     env = dict(os.environ, RANK='0', LOCAL_RANK='0', WORLD_SIZE='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(_free_port()),
                T2O_OWN_COMM='1', T2O_BENCH_DETAIL_DIR=str(tmp_path), HSA_ENABLE_IPC_MODE_LEGACY='0')
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--quick',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--full', '--quick',
                         '--no-cpu-baseline', '--exec-steps', '5', '--exec-warmup', '2'], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1]
@@ -37,6 +37,47 @@ def test_one_rank_job_with_the_c_abi_allreduce_on_the_timed_path(tmp_path):
     with open(os.path.join(str(tmp_path), 'bench_detail.json')) as f:
         detail = json.load(f)
     assert detail['train_step']['parameters_finite'] is True
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` runs the train step alone (no --full legs in the line), times exactly K steps,
+    and --dump-outputs writes the last timed step's loss and a sample of the model it updated as float32 .npy files -- the same
+    files in a second run with the same arguments."""
+    import numpy as np
+    env = dict(os.environ, T2O_BENCH_DETAIL_DIR=str(tmp_path))
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
+        env.pop(k, None)
+    out = tmp_path / 'outputs'
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+                        '--dump-outputs', str(out)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d['steps'] == 2 and d['warmup'] == 1
+    with open(os.path.join(str(tmp_path), 'bench_detail.json')) as f:
+        assert json.load(f)['train_step']['steps'] == 2
+    assert d['value'] > 0 and d['ms_per_step'] > 0 and d['unit'] == 'images/sec' and d['higher_is_better'] is True and d['dtype'] == 'f32'
+    assert abs(d['value'] - 64 * 1e3 / d['ms_per_step']) < 0.01 * d['value']
+    for k in ('executor', 'roofline', 'cpu_baseline', 'train_step_128', 'parity'):
+        assert k not in d, k
+    assert 'supervised_ms' not in d['train_step']
+    total = 0
+    for name in ('loss', 'params', 'grads', 'bn_stats'):
+        a = np.load(str(out / (name + '.npy')))
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), name
+        total += a.nbytes
+    assert total < 64 << 20
+    assert abs(float(np.load(str(out / 'loss.npy'))[0]) - d['train_step']['loss']) < 1e-6
+    # the same arguments: the same inputs, and (the train legs run on the framework's deterministic implementations) the same
+    # outputs -- the same files, shapes and dtypes, finite, equal
+    again = tmp_path / 'again'
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+                        '--dump-outputs', str(again)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert sorted(os.listdir(str(again))) == sorted(os.listdir(str(out)))
+    for name in ('loss', 'params', 'grads', 'bn_stats'):
+        a, b = np.load(str(out / (name + '.npy'))), np.load(str(again / (name + '.npy')))
+        assert a.shape == b.shape and a.dtype == b.dtype and np.isfinite(b).all(), name
+        assert np.array_equal(a, b), (name, float(np.abs(a - b).max()))
 
 
 _TWO_RANK_WORKER = r'''

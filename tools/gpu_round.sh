@@ -3,7 +3,7 @@
 #   tools/gpu_round.sh <tag> <stage> [<stage> ...]
 # Logs -> gpurun_out/<tag>/ (copy what is to be judged to profiles/).  Stages, run in the order given:
 #   test[:<pytest args>]  pytest -m gpu (default: all of tests/)        smoke        __graft_entry__.smoke()
-#   bench                 default bench.py (+ bench_detail.json)         benchprof    rocprofv3 --kernel-trace --stats of the same command
+#   bench                 bench.py --full (+ bench_detail.json)          benchprof    rocprofv3 --kernel-trace --stats of the same command
 #   step[:<graph 0|1>]    rocprofv3 kernel stats + trace gaps of the train step alone (tools/step_only.py)
 #   seq                   ordered kernel list of one train step (tools/step_sequence.py)
 #   hip                   rocprofv3 --hip-trace --stats of the eager step
@@ -30,12 +30,12 @@ for stage in "$@"; do
     smoke)
       timeout 300 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -n 2 $OUT/smoke.log ;;
     bench)
-      timeout 1500 python bench.py $arg > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+      timeout 1500 python bench.py --full $arg > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
       cp bench_detail.json $OUT/bench_detail.json 2>/dev/null
       tail -n 1 $OUT/bench.json | wc -c; python tools/bench_summary.py $OUT/bench.json $OUT/bench_detail.json | head -60; tail -n 3 $OUT/bench.err ;;
     benchprof)
       cd /tmp
-      timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/prof -- python $ROOT/bench.py --no-cpu-baseline --no-128 $arg > $ROOT/$OUT/prof_bench.json 2> $ROOT/$OUT/prof.err; echo "rocprof rc=$?"
+      timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/prof -- python $ROOT/bench.py --full --no-cpu-baseline --no-128 $arg > $ROOT/$OUT/prof_bench.json 2> $ROOT/$OUT/prof.err; echo "rocprof rc=$?"
       cd $ROOT
       find $OUT/prof -name "*kernel_stats*.csv" | head -1 | xargs -r -I{} cp {} $OUT/bench_kernel_stats.csv
       rm -rf $OUT/prof; head -n 14 $OUT/bench_kernel_stats.csv | cut -c1-160 ;;
