@@ -182,6 +182,25 @@ int t2o_op_candidates_multi_l1(const int* ops, const int* img_index, int J, cons
                                const float* target, const float* params, int C, int param_stride, float* loss,
                                void* workspace, size_t workspace_bytes, int H, int W, void* stream);
 
+/* ---- planner parameter fits, batched and device resident (utils/beam_search.py:65-91,148-167: one minimisation per
+ * candidate step, one executor call and one host sync per objective evaluation).  Adam on the parameters of up to 64
+ * jobs at once; job j fits operator ops[j] (0, 1, 2, 3, 5 or 6) so that
+ *     mean |clamp(process(imgs[img_index[j]], params[j])) - targets[target_index[j]]|
+ * becomes small.  ops / img_index / target_index are HOST arrays (copied into the kernel arguments); imgs (n_img,3,H,W),
+ * targets (n_target,3,H,W) and params (J,24: start values in, fitted values out, in place) are device memory; dist (J)
+ * receives the loss at the returned parameters.  Two launches per iteration, none of them waits on the host; nothing
+ * is allocated: Adam's moments, the per-job stop state and the per-workgroup partial sums live in `workspace`
+ * (t2o_fit_multi_workspace_bytes, 8-byte aligned).  The update is torch.optim.Adam's (bias corrected, no weight decay,
+ * no projection onto the operator's range).  Stop rule, per job on the device: at iterations check_every,
+ * 2 check_every, ... a job whose loss fell by less than tol since its previous check stops moving (the first check only
+ * records the loss); check_every <= 0 disables it.  Deterministic: fixed summation order, no atomics; a job's result
+ * does not depend on the other jobs of the call.  Any H, W. */
+size_t t2o_fit_multi_workspace_bytes(int J, int H, int W);
+int t2o_fit_multi_l1_adam(const int* ops, const int* img_index, const int* target_index, int J, const float* imgs,
+                          int n_img, const float* targets, int n_target, float* params, float* dist, void* workspace,
+                          size_t workspace_bytes, int H, int W, int steps, double lr, double beta1, double beta2,
+                          double eps, int check_every, double tol, void* stream);
+
 /* ---- SSIM: utils/ssim/__init__.py:20-40 (forward: the evaluation metric; backward: its closed-form gradient) ----
  * 11x11 Gaussian window (sigma 1.5), zero padding, C1 = 1e-4, C2 = 9e-4.
  * out[b] = mean over (C,H,W) of the SSIM map of sample b (size_average=False of the reference;

@@ -18,6 +18,7 @@ _P = ctypes.c_void_p
 _I = ctypes.c_int
 _Z = ctypes.c_size_t
 _F = ctypes.c_float
+_D = ctypes.c_double
 
 # name -> (restype, argtypes); must list every function declared in include/t2onet_hip.h
 SIGNATURES = {
@@ -44,6 +45,8 @@ SIGNATURES = {
     't2o_op_candidates_l1': (_I, [_I, _P, _P, _P, _I, _I, _P, _P, _Z, _I, _I, _P]),
     't2o_candidates_multi_workspace_bytes': (_Z, [_I, _I, _I, _I]),
     't2o_op_candidates_multi_l1': (_I, [c_i, c_i, _I, _P, _I, _P, _P, _I, _I, _P, _P, _Z, _I, _I, _P]),
+    't2o_fit_multi_workspace_bytes': (_Z, [_I, _I, _I]),
+    't2o_fit_multi_l1_adam': (_I, [c_i, c_i, c_i, _I, _P, _I, _P, _I, _P, _P, _P, _Z, _I, _I, _I, _D, _D, _D, _D, _I, _D, _P]),
     't2o_ssim_workspace_bytes': (_Z, [_I, _I, _I, _I]),
     't2o_ssim_fwd': (_I, [_P, _P, _P, _P, _Z, _I, _I, _I, _I, _P]),
     't2o_ssim_bwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

@@ -974,6 +974,44 @@ def candidates_multi_l1(ops, img_index, imgs, target, params):
     return loss
 
 
+FIT_MAX_JOBS = 64
+
+
+def fit_multi_l1(ops, img_index, imgs, targets, target_index, params0, steps=300, lr=2e-2, check_every=50, tol=1e-6,
+                 betas=(0.9, 0.999), eps=1e-8):
+    """Adam on the parameters of J <= 64 jobs at once, entirely on the device (t2o_fit_multi_l1_adam): job j fits
+    operator ops[j] on imgs[img_index[j]] against targets[target_index[j]] under mean |execute - target|, starting
+    from params0[j].  ops / img_index / target_index: python ints; imgs (n,3,H,W); targets (m,3,H,W); params0 (J,n<=24).
+    torch.optim.Adam's update and the serial fit's stop rule (check_every <= 0: none), two launches per iteration, no
+    host synchronisation.  Returns (params (J,24) zero padded, dist (J,) = the loss at those parameters)."""
+    _need_gpu(imgs, targets, params0)
+    imgs = imgs.detach().reshape(-1, 3, *imgs.shape[-2:]).contiguous()
+    targets = targets.detach().reshape(-1, 3, *targets.shape[-2:]).contiguous()
+    if imgs.shape[-2:] != targets.shape[-2:]:
+        raise ValueError('images and targets must have one size')
+    J = len(ops)
+    if not (len(img_index) == len(target_index) == J == params0.shape[0]) or params0.dim() != 2 or params0.shape[1] > PARAM_PAD:
+        raise ValueError('one (operator, image index, target index, parameter row of at most 24) per job')
+    H, W = imgs.shape[-2:]
+    dev = imgs.device
+    if params0.shape[1] == PARAM_PAD:
+        params = params0.detach().contiguous().clone()                   # (a device copy, no kernel)
+    else:
+        params = torch.zeros(J, PARAM_PAD, dtype=torch.float32, device=dev)
+        params[:, :params0.shape[1]] = params0.detach()
+    dist = torch.empty(J, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    ws = torch.empty(max(lib.t2o_fit_multi_workspace_bytes(J, H, W), 8), dtype=torch.uint8, device=dev)
+    c_ops = (ctypes.c_int * max(J, 1))(*[int(o) for o in ops])
+    c_img = (ctypes.c_int * max(J, 1))(*[int(i) for i in img_index])
+    c_tgt = (ctypes.c_int * max(J, 1))(*[int(i) for i in target_index])
+    rc = lib.t2o_fit_multi_l1_adam(c_ops, c_img, c_tgt, J, _ptr(imgs), imgs.shape[0], _ptr(targets), targets.shape[0],
+                                   _ptr(params), _ptr(dist), _ptr(ws), ws.numel(), H, W, int(steps), float(lr),
+                                   float(betas[0]), float(betas[1]), float(eps), int(check_every), float(tol), _stream(dev))
+    _lib.check(rc, 't2o_fit_multi_l1_adam')
+    return params, dist
+
+
 class _SsimFn(torch.autograd.Function):
     """out (B) = per-sample mean of the SSIM map; backward = t2o_ssim_bwd (closed form, one launch)."""
 

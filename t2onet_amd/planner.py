@@ -12,6 +12,12 @@ host sync (`get_param_naive`, beam_search.py:65-91).  Same surface here (`get_pa
                       host sync per beam step instead of one per candidate fit;
                       curve operators (8 / 24 parameters) and sharpness: Adam on the fused
                       operator+L1 forward/backward kernels with no per-iteration sync.
+  optimizer='batched' the same sweep for the 1-parameter operators; EVERY other candidate of a beam step -- curve
+                      operators, sharpness, all beams -- in one device-resident Adam solve (fit_adam_batch ->
+                      t2o_fit_multi_l1_adam: two launches per iteration for all jobs together, stop rule on the
+                      device): one host sync for the sweep fits and one for the Adam fits per beam step.
+                      beam_search_pairs runs that search for several same-size pairs in lock-step, the Adam fits
+                      of all pairs sharing launches (what plan_cli generates FiveK action sets with).
   'Nelder-Mead' | 'adam' | 'lbfgs'  the reference's procedures, objective evaluated by the HIP kernels.
 
 Only dist_type 'L1' is supported (the discriminator distances belong to the out-of-scope
@@ -83,6 +89,32 @@ def fit_sweep_batch(images, jobs, target, executor, rounds=3):
     return best, best_loss.view(-1)
 
 
+def fit_adam_batch(images, jobs, targets, executor, steps=300, lr=2e-2, check_every=50, tol=1e-6):
+    """Adam fits of many jobs at once, the sibling of fit_sweep_batch for operators of any parameter count.  images:
+    list of (1,3,H,W); targets: list of (1,3,H,W) of that size (or one tensor); jobs: list of (image index, operation)
+    -- target 0 -- or (image index, operation, target index).  Start values, step size and stop rule are _fit_adam's as
+    'sweep' uses it.  Returns (params (J,24) zero padded, dists (J,)) on the device -- no host synchronisation here;
+    more than 64 jobs go in chunks of 64 (the kernel's limit), which does not change any job's result."""
+    targets = [targets] if torch.is_tensor(targets) else list(targets)
+    dev = targets[0].device
+    imgs = torch.cat([im.reshape(1, 3, *im.shape[-2:]) for im in images], 0)
+    tgts = torch.cat([t.reshape(1, 3, *t.shape[-2:]) for t in targets], 0)
+    jobs = [(jb[0], jb[1], jb[2] if len(jb) > 2 else 0) for jb in jobs]
+    start = torch.zeros(len(jobs), T.PARAM_PAD)
+    for k, (_, op, _) in enumerate(jobs):
+        p0 = _initial_param(op, executor)
+        start[k, :p0.numel()] = p0
+    start = start.to(dev)
+    out_p, out_d = [], []
+    for c0 in range(0, len(jobs), T.FIT_MAX_JOBS):
+        chunk = jobs[c0:c0 + T.FIT_MAX_JOBS]
+        p, d = T.fit_multi_l1([jb[1] for jb in chunk], [jb[0] for jb in chunk], imgs, tgts, [jb[2] for jb in chunk],
+                              start[c0:c0 + T.FIT_MAX_JOBS], steps=steps, lr=lr, check_every=check_every, tol=tol)
+        out_p.append(p)
+        out_d.append(d)
+    return (out_p[0], out_d[0]) if len(out_p) == 1 else (torch.cat(out_p), torch.cat(out_d))
+
+
 def _fit_adam(I0, I1, operation, executor, param0, steps=300, lr=2e-2, check_every=50, tol=1e-6):
     """Adam on the operator's parameters against mean |execute(I0) - I1| (beam_search.py:65-91 with a first-order
     optimiser).  One library call per iteration: executor.value_and_grad (loss + parameter gradient, no separate forward,
@@ -122,8 +154,13 @@ def get_param(I0, I1, txt, operation, executor, discriminator=None, dist_type='L
     param0 = _initial_param(operation, executor)
     if optimizer == 'Nelder-Mead':
         return _fit_scipy(I0, I1, operation, executor, param0, 'Nelder-Mead')
-    if optimizer == 'sweep' and operation in PER_PIXEL_SWEEP_OPS:
+    if optimizer in ('sweep', 'batched') and operation in PER_PIXEL_SWEEP_OPS:
         return _fit_sweep_1d(I0, I1, operation, executor)
+    if optimizer == 'batched':
+        if I0.shape[0] != 1:
+            raise ValueError("optimizer='batched' fits one image pair per job")
+        params, _ = fit_adam_batch([I0], [(0, operation)], [I1], executor)
+        return params[:, :param0.numel()].clone(), True
     if optimizer in ('sweep', 'adam'):
         lr = 1e-2 if optimizer == 'adam' else 2e-2
         return _fit_adam(I0, I1, operation, executor, param0.view(1, -1).repeat(I0.shape[0], 1), lr=lr)
@@ -141,60 +178,140 @@ def get_param(I0, I1, txt, operation, executor, discriminator=None, dist_type='L
     raise ValueError('unknown optimizer %r' % (optimizer,))
 
 
+class _Beam:
+    """The beam of one image pair (beam_search.py:196-264): surviving sequences, their images, the early exit."""
+
+    def __init__(self, I_0, I_gt, beam_size, operations, operation_names, err, replace):
+        self.I_gt, self.beam_size, self.operations, self.names, self.err, self.replace = I_gt, beam_size, operations, operation_names, err, replace
+        self.min_dist = float('inf')
+        self.sequences = [[[], float('inf')]]
+        self.I_buff = [I_0]
+        self.done = False
+
+    def candidates(self):
+        """(beam, operation) pairs of this step, in the reference's visiting order."""
+        pairs = []
+        for j in range(len(self.I_buff)):
+            used = [self.names.index(v[0]) for v in self.sequences[j][0]]
+            pairs += [(j, operation) for operation in self.operations if self.replace or operation not in used]
+        return pairs
+
+    def advance(self, pairs, fitted, fit_one, executor):
+        """One step.  fitted: {(beam, operation): (param (1,n), dist)} from the batched fits -- their images are executed
+        only if they enter the beam; every other pair is fitted by fit_one(I, operation) -> param."""
+        all_candidates, I_tmp_list, tmp_min_dists = [], [], []
+        no_update, finished = True, False
+        for j, operation in pairs:
+            I = self.I_buff[j]
+            if (j, operation) in fitted:
+                param, dist = fitted[(j, operation)]
+                I_out = None
+            else:
+                param = fit_one(I, operation)
+                I_out = execute(I, operation, param, executor)
+                dist = get_dist(I_out, self.I_gt).item()
+            if dist < self.min_dist:
+                if I_out is None:
+                    I_out = execute(I, operation, param, executor)
+                tmp_min_dists.append(dist)
+                all_candidates.append([self.sequences[j][0] + [(self.names[operation], param[0].tolist(), dist, I_out)], dist])
+                I_tmp_list.append(I_out)
+                no_update = False
+                finished = finished or dist < self.err
+        self.min_dist = min(tmp_min_dists) if tmp_min_dists else self.min_dist
+        if len(all_candidates) < self.beam_size:
+            all_candidates += self.sequences
+            I_tmp_list += self.I_buff
+        order = np.argsort(np.array([v[1] for v in all_candidates]))
+        self.sequences = [all_candidates[i] for i in order][:self.beam_size]
+        self.I_buff = [I_tmp_list[i] for i in order][:self.beam_size]
+        self.done = no_update or finished
+
+    def result(self):
+        actions = [[act[:-1] for act in seq[0]] for seq in self.sequences]
+        Is = [[act[-1] for act in seq[0]] for seq in self.sequences]
+        return actions, Is
+
+
+def _sweep_fits(beam, pairs, executor, fitted):
+    """The 1-parameter candidates of a step through the batched sweep: one host sync per 64 jobs."""
+    batch = [pr for pr in pairs if pr[1] in PER_PIXEL_SWEEP_OPS]
+    for c0 in range(0, len(batch), 64):                                  # (the kernel takes 64 jobs per launch)
+        chunk = batch[c0:c0 + 64]
+        params, dists = fit_sweep_batch(beam.I_buff, chunk, beam.I_gt, executor)
+        params, dists = params.cpu(), dists.cpu()                        # the one host sync of these fits
+        for k, pr in enumerate(chunk):
+            fitted[pr] = (params[k:k + 1].to(beam.I_gt.device), float(dists[k]))
+
+
+def _adam_fits(beams, pairs_of, executor, fitted_of):
+    """Every candidate of this step that the sweep does not take, of all beams of all pairs, in one fit_adam_batch:
+    one host sync."""
+    images, jobs, owner = [], [], []
+    for t, (beam, pairs) in enumerate(zip(beams, pairs_of)):
+        base = len(images)
+        images += beam.I_buff
+        for pr in pairs:
+            if pr[1] not in PER_PIXEL_SWEEP_OPS:
+                jobs.append((base + pr[0], pr[1], t))
+                owner.append((t, pr))
+    if not jobs:
+        return
+    params, dists = fit_adam_batch(images, jobs, [beam.I_gt for beam in beams], executor)
+    params, dists = params.cpu(), dists.cpu()                            # the one host sync of these fits
+    for k, (t, pr) in enumerate(owner):
+        n = executor.get_param_num(pr[1])
+        fitted_of[t][pr] = (params[k:k + 1, :n].to(beams[t].I_gt.device), float(dists[k]))
+
+
+def _check_l1(dist_type, discriminator, who):
+    if dist_type != 'L1' or discriminator is not None:
+        # (checked before any fit: the batched fits score candidates with the L1 kernels directly and would otherwise
+        # answer a non-L1 request with L1 distances)
+        raise NotImplementedError('%s: L1 distance without a discriminator only (the FiveK planner, beam_search.py:196-264)' % who)
+
+
 def beam_search(I_0, I_gt, txt, executor, discriminator, beam_size, operations, operation_names, max_step, err,
                 dist_type='L1', optimizer='sweep', replace=False):
     """Beam search over operator sequences (beam_search.py:196-264).  Returns (actions, Is):
     per surviving sequence the list of (name, param list, dist) and the list of intermediate images."""
-    if dist_type != 'L1' or discriminator is not None:
-        # (checked here, before any fit: the batched sweep below scores candidates with the L1 kernels directly and
-        # would otherwise answer a non-L1 request with L1 distances for the one-parameter operators)
-        raise NotImplementedError('beam_search: L1 distance without a discriminator only (the FiveK planner, beam_search.py:196-264)')
-    min_dist = float('inf')
-    sequences = [[[], float('inf')]]
-    I_buff = [I_0]
+    _check_l1(dist_type, discriminator, 'beam_search')
+    beam = _Beam(I_0, I_gt, beam_size, operations, operation_names, err, replace)
+
+    def fit_one(I, operation):
+        return get_param(I, I_gt, txt, operation, executor, None, dist_type, optimizer)[0]
     for _ in range(max_step):
-        all_candidates, I_tmp_list, tmp_min_dists = [], [], []
-        no_update, finished = True, False
-        # candidate (beam, operation) pairs of this step, in the reference's visiting order
-        pairs = []
-        for j in range(len(I_buff)):
-            used = [operation_names.index(v[0]) for v in sequences[j][0]]
-            pairs += [(j, operation) for operation in operations if replace or operation not in used]
+        pairs = beam.candidates()
         fitted = {}
-        if optimizer == 'sweep':
-            batch = [pr for pr in pairs if pr[1] in PER_PIXEL_SWEEP_OPS]
-            for c0 in range(0, len(batch), 64):                              # (the kernel takes 64 jobs per launch)
-                chunk = batch[c0:c0 + 64]
-                params, dists = fit_sweep_batch(I_buff, chunk, I_gt, executor)
-                params, dists = params.cpu(), dists.cpu()                    # the one host sync of these fits
-                for k, pr in enumerate(chunk):
-                    fitted[pr] = (params[k:k + 1].to(I_gt.device), float(dists[k]))
-        for j, operation in pairs:
-            I = I_buff[j]
-            if (j, operation) in fitted:
-                param, dist = fitted[(j, operation)]
-                I_out = None                                                 # executed below only if it enters the beam
-            else:
-                param, _ = get_param(I, I_gt, txt, operation, executor, None, dist_type, optimizer)
-                I_out = execute(I, operation, param, executor)
-                dist = get_dist(I_out, I_gt, dist_type).item()
-            if dist < min_dist:
-                if I_out is None:
-                    I_out = execute(I, operation, param, executor)
-                tmp_min_dists.append(dist)
-                all_candidates.append([sequences[j][0] + [(operation_names[operation], param[0].tolist(), dist, I_out)], dist])
-                I_tmp_list.append(I_out)
-                no_update = False
-                finished = finished or dist < err
-        min_dist = min(tmp_min_dists) if tmp_min_dists else min_dist
-        if len(all_candidates) < beam_size:
-            all_candidates += sequences
-            I_tmp_list += I_buff
-        order = np.argsort(np.array([v[1] for v in all_candidates]))
-        sequences = [all_candidates[i] for i in order][:beam_size]
-        I_buff = [I_tmp_list[i] for i in order][:beam_size]
-        if no_update or finished:
+        if optimizer in ('sweep', 'batched'):
+            _sweep_fits(beam, pairs, executor, fitted)
+        if optimizer == 'batched':
+            _adam_fits([beam], [pairs], executor, [fitted])
+        beam.advance(pairs, fitted, fit_one, executor)
+        if beam.done:
             break
-    actions = [[act[:-1] for act in seq[0]] for seq in sequences]
-    Is = [[act[-1] for act in seq[0]] for seq in sequences]
-    return actions, Is
+    return beam.result()
+
+
+def beam_search_pairs(inputs, targets, txt, executor, discriminator, beam_size, operations, operation_names, max_step, err,
+                      dist_type='L1', replace=False):
+    """beam_search(..., optimizer='batched') for P image pairs of one size in lock-step: every pair keeps its own beam
+    and its own early exit, the sweeps run per pair, and the multi-parameter fits of all pairs of a step share one
+    fit_adam_batch (64 jobs per launch).  inputs / targets: lists of (1,3,H,W).  Returns [(actions, Is)] per pair,
+    each exactly what the single-pair search returns."""
+    _check_l1(dist_type, discriminator, 'beam_search_pairs')
+    if len(inputs) != len(targets):
+        raise ValueError('one target per input')
+    beams = [_Beam(I_0, I_gt, beam_size, operations, operation_names, err, replace) for I_0, I_gt in zip(inputs, targets)]
+    for _ in range(max_step):
+        live = [beam for beam in beams if not beam.done]
+        if not live:
+            break
+        pairs_of = [beam.candidates() for beam in live]
+        fitted_of = [{} for _ in live]
+        for beam, pairs, fitted in zip(live, pairs_of, fitted_of):
+            _sweep_fits(beam, pairs, executor, fitted)
+        _adam_fits(live, pairs_of, executor, fitted_of)
+        for beam, pairs, fitted in zip(live, pairs_of, fitted_of):
+            beam.advance(pairs, fitted, None, executor)
+    return [beam.result() for beam in beams]
