@@ -701,6 +701,26 @@ int t2o_wino_fused_conv_bnsums_nhwc(const float* x, const float* uc, float* y, c
                                     const float* save_invstd, const float* weight, const float* bias, float* rows,
                                     const float* zeros, int N, int H, int W, int Ci, int Co, void* stream);
 
+/* ---- the data step's pixel work (t2o_image_io.hip): utils/visual_utils.py:6-58.
+ * t2o_resize_u8_to_f32: what the reference's loaders do after decoding (visual_utils.py:6-47: cv2.resize, the channel
+ * transpose, / 255) for a whole batch in ONE launch.  src: DEVICE bytes holding n uint8 (h,w,3) RGB images of differing
+ * sizes at arbitrary byte offsets (no alignment needed); descs: DEVICE table of n descriptors, 8-byte aligned; out:
+ * (n,3,out_h,out_w) fp32.  out[i] = resize(image i).astype(float32).transpose(2,0,1) / 255 with OpenCV's 8-bit INTER_LINEAR
+ * as t2onet_amd/data.py:resize_linear_u8 states it (fp64 half-pixel taps, 11-bit coefficients rounded half to even, int32
+ * passes; a source of the output's size is converted as is, an exact 2x shrink is the rounded 2x2 block mean) -- bit for
+ * bit.  A descriptor with h = w = 0 stands for an absent image: out[i] = 0 (the unused steps of a planned sequence,
+ * datasets/FiveKdataset.py:118-130).  The caller guarantees offset + 3 h w <= the size of src: descriptors live on the
+ * device and are not read back.
+ * t2o_f32_to_u8_hwc: tensor2img (visual_utils.py:50-58) for a batch: img (n,3,h,w) fp32 in [0,1] -> out (n,h,w,3) uint8 =
+ * img * 255 truncated; any h, w and any alignment of out. */
+typedef struct {
+  long long offset;   /* first byte of the image, counted from src */
+  int h, w;           /* rows and columns of the source; 0, 0 = absent */
+} t2o_image_desc_t;
+int t2o_resize_u8_to_f32(const unsigned char* src, const t2o_image_desc_t* descs, int n, int out_h, int out_w, float* out,
+                         void* stream);
+int t2o_f32_to_u8_hwc(const float* img, int n, int h, int w, unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

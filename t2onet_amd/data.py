@@ -95,12 +95,24 @@ def resize_linear_u8(img, out_h, out_w):
     return np.clip(out, 0, 255).astype(np.uint8)
 
 
+def decode_image(path):
+    """The decoded file as a uint8 (H,W,3) RGB array (PIL / libjpeg, like cv2's decoder): everything the loaders do
+    before the resize.  This part stays on the host; `raw=True` datasets hand it on as it is."""
+    from PIL import Image
+    return np.asarray(Image.open(path).convert('RGB'), dtype=np.uint8)
+
+
+def short_side_size(h, w, short_size=600):
+    """(h_new, w_new) of utils/visual_utils.py:34-47: the short side scaled to `short_size`."""
+    ratio = short_size / min(h, w)
+    return int(np.round(h * ratio)), int(np.round(w * ratio))
+
+
 def load_image(path, size=None):
     """RGB float tensor (3,H,W) in [0,1] as the reference's loaders produce it (utils/visual_utils.py:6-31:
     cv2.imread -> cv2.resize -> BGR->RGB -> /255).  `size`: None (as is), an int (square, training:
     load_train_img) or (h, w).  Decoding is PIL's (libjpeg, like cv2's); the resize is resize_linear_u8."""
-    from PIL import Image
-    img = np.asarray(Image.open(path).convert('RGB'), dtype=np.uint8)
+    img = decode_image(path)
     if size is not None:
         h, w = (size, size) if isinstance(size, int) else size
         img = resize_linear_u8(img, h, w)
@@ -109,11 +121,8 @@ def load_image(path, size=None):
 
 def load_image_short_side(path, short_size=600):
     """utils/visual_utils.py:34-47 (full-resolution inference): the short side scaled to `short_size`."""
-    from PIL import Image
-    img = np.asarray(Image.open(path).convert('RGB'), dtype=np.uint8)
-    h, w = img.shape[:2]
-    ratio = short_size / min(h, w)
-    img = resize_linear_u8(img, int(np.round(h * ratio)), int(np.round(w * ratio)))
+    img = decode_image(path)
+    img = resize_linear_u8(img, *short_side_size(img.shape[0], img.shape[1], short_size))
     return torch.from_numpy(img.astype(np.float32).transpose(2, 0, 1) / 255.0)
 
 
@@ -138,10 +147,12 @@ def txt2idx(sent, vocab2id, max_len):
 class FiveKAct(Dataset):
     """(img_x, img_ys (6,3,S,S), req_idx, ops (7,), params (5,24), req) per item, like
     datasets/FiveKdataset.py:67-135.  Directory layout as the reference's:
-    anno_dir/{phase}_sess_{session}.json, act_dir/{phase}{i}/{i:05d}.json + edit{k}.jpg."""
+    anno_dir/{phase}_sess_{session}.json, act_dir/{phase}{i}/{i:05d}.json + edit{k}.jpg.
+    raw=True: the images stay as decoded -- img_x a uint8 (H,W,3) array, img_ys a list of 6 such arrays with None in the
+    unused steps -- for collate_raw + device_batch, which resize them on the GPU."""
 
-    def __init__(self, img_dir, anno_dir, act_dir, phase='train', session=1, train_img_size=128):
-        self.img_dir, self.act_dir, self.phase, self.size = img_dir, act_dir, phase, train_img_size
+    def __init__(self, img_dir, anno_dir, act_dir, phase='train', session=1, train_img_size=128, raw=False):
+        self.img_dir, self.act_dir, self.phase, self.size, self.raw = img_dir, act_dir, phase, train_img_size, raw
         with open(os.path.join(anno_dir, '{}_sess_{}.json'.format(phase, session))) as f:
             self.data = json.load(f)
 
@@ -153,6 +164,11 @@ class FiveKAct(Dataset):
         item_dir = os.path.join(self.act_dir, '{}{}'.format(self.phase, item))
         with open(os.path.join(item_dir, '{:05d}.json'.format(item))) as f:
             ops, params, n = parse_action_record(json.load(f))
+        if self.raw:
+            imgs = [decode_image(os.path.join(item_dir, 'edit{}.jpg'.format(k))) for k in range(n)] + [None] * (OP_MAX_LEN - n)
+            imgs.append(decode_image(os.path.join(self.img_dir, dic['output'])))
+            img_x = decode_image(os.path.join(self.img_dir, dic['input']))
+            return img_x, imgs, np.array(dic['request_idx']), ops, params, dic['request']
         imgs = torch.zeros(OP_MAX_LEN + 1, 3, self.size, self.size)
         for k in range(n):
             imgs[k] = load_image(os.path.join(item_dir, 'edit{}.jpg'.format(k)), self.size)
@@ -164,10 +180,11 @@ class FiveKAct(Dataset):
 class FiveK(Dataset):
     """(img_x, img_y, req_idx, req) per item with NO planned actions, like datasets/FiveKdataset.py:24-52: the split the
     reference validates and tests on (train_seq2seqL1.py:155-156, batch_size=1).  phase 'train': square training size;
-    any other phase: full resolution with the short side scaled to 600 pixels (load_infer_img_short_size_bounded)."""
+    any other phase: full resolution with the short side scaled to 600 pixels (load_infer_img_short_size_bounded).
+    raw=True: both images stay uint8 (H,W,3) arrays as decoded (collate_raw + device_batch resize them on the GPU)."""
 
-    def __init__(self, img_dir, anno_dir, phase='val', session=1, train_img_size=128, short_size=600):
-        self.img_dir, self.phase, self.size, self.short_size = img_dir, phase, train_img_size, short_size
+    def __init__(self, img_dir, anno_dir, phase='val', session=1, train_img_size=128, short_size=600, raw=False):
+        self.img_dir, self.phase, self.size, self.short_size, self.raw = img_dir, phase, train_img_size, short_size, raw
         with open(os.path.join(anno_dir, '{}_sess_{}.json'.format(phase, session))) as f:
             self.data = json.load(f)
 
@@ -176,11 +193,75 @@ class FiveK(Dataset):
 
     def _load(self, name):
         path = os.path.join(self.img_dir, name)
+        if self.raw:
+            return decode_image(path)
         return load_image(path, self.size) if self.phase == 'train' else load_image_short_side(path, self.short_size)
 
     def __getitem__(self, item):
         dic = self.data[item]
         return self._load(dic['input']), self._load(dic['output']), np.array(dic['request_idx']), dic['request']
+
+
+def collate_raw(items):
+    """collate_fn of a DataLoader over a raw=True dataset: every image of the batch packed back to back into one byte
+    buffer headed by its descriptor table (functional.pack_u8), in the order of device_batch's output -- all img_x first,
+    then item by item the 6 img_ys (FiveKAct; an unused step is an absent descriptor, h = w = 0) or the img_y (FiveK).
+    Returns {'buffer': uint8 tensor, 'descs': (n,4) int32 tensor = the table, 'items': B, 'rest': the default collation of
+    the items' other fields}.  Unpinned (it runs in workers): DataLoader(pin_memory=True) pins it."""
+    from torch.utils.data import default_collate
+    from . import functional as T
+    act = len(items[0]) == 6
+    images = [it[0] for it in items]
+    if act:
+        images += [im for it in items for im in it[1]]
+    else:
+        images += [it[1] for it in items]
+    buffer, descs = T.pack_u8(images, pin=False)
+    table = torch.from_numpy(descs.view(np.int32).reshape(-1, 4).copy())
+    return {'buffer': buffer, 'descs': table, 'items': len(items), 'rest': default_collate([tuple(it[2:]) for it in items])}
+
+
+def device_batch(batch, size=None, device=None, short_size=None, images_only=False):
+    """A collate_raw batch as exactly the tensors the default DataLoader batch of the same items holds, on the device:
+    [img_x, img_ys (B,6,3,S,S), req_idx, ops, params, reqs] (FiveKAct) or [img_x, img_y, req_idx, reqs] (FiveK).  One
+    upload of the packed bytes and one resize launch (functional.resize_u8) replace the per-image host resizes.
+    size: int or (h, w) -- every image resized to it.  short_size (instead of size): FiveK(phase != 'train'), one item
+    per batch as the reference evaluates: each image to short_side_size of its own shape, one launch of N = 1 per image.
+    images_only: leave the other tensors where the collation put them (the train loop reads lengths on the host)."""
+    from . import functional as T
+    B = batch['items']
+    if device is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    if short_size is None:
+        out = T.resize_u8((batch['buffer'], batch['descs']), size, device)
+        img_x, second = out[:B], out[B:]
+        if second.shape[0] != B:
+            second = second.view(B, second.shape[0] // B, *second.shape[1:])
+    else:
+        if B != 1:
+            raise ValueError('device_batch: the short-side form takes one item per batch (images of differing sizes)')
+        dev_buffer, table_ptr, descs, keep = T.upload_packed(batch['buffer'], batch['descs'], device)
+        if descs.size != 2:
+            raise ValueError('device_batch: the short-side form serves FiveK items (img_x, img_y)')
+        outs = [T._resize_launch(dev_buffer, table_ptr + i * T.IMAGE_DESC.itemsize, 1,
+                                 *short_side_size(int(descs['h'][i]), int(descs['w'][i]), short_size)) for i in range(2)]
+        img_x, second = outs
+    rest = [v if images_only or not torch.is_tensor(v) else v.to(device, non_blocking=True) for v in batch['rest']]
+    return [img_x, second] + rest
+
+
+class DeviceBatches(object):
+    """A DataLoader of collate_raw batches, iterated as device_batch(...) results."""
+
+    def __init__(self, loader, size=None, device=None, short_size=None, images_only=False):
+        self.loader, self.kw = loader, dict(size=size, device=device, short_size=short_size, images_only=images_only)
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        for batch in self.loader:
+            yield device_batch(batch, **self.kw)
 
 
 class SyntheticFiveK(Dataset):

@@ -7,6 +7,7 @@ import ctypes
 
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1730,3 +1731,129 @@ def conv3x3_winograd(x, weight, addend=None):
     ad = None if addend is None else addend.permute(0, 2, 3, 1).contiguous()
     y, _ = wino_conv_nhwc(xh, U, N, H, W, ad)
     return y.permute(0, 3, 1, 2)
+
+
+# ---- image I/O (t2o_image_io.hip): the data step's resize + layout conversion, and its inverse for writing images ----
+
+IMAGE_DESC = np.dtype([('offset', '<i8'), ('h', '<i4'), ('w', '<i4')])       # t2o_image_desc_t, field for field
+
+
+def _u8_hwc(img):
+    a = img.numpy() if torch.is_tensor(img) else np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError('image must be uint8 (H,W,3), got %s %s' % (a.dtype, a.shape))
+    return np.ascontiguousarray(a)
+
+
+def pack_u8(images, pads=None, pin=None):
+    """Pack uint8 (H,W,3) images (arrays or CPU tensors; None = an absent image, a zero output) back to back into ONE
+    byte buffer headed by their descriptor table.  Returns (buffer, descs): a 1-D uint8 CPU tensor -- pinned when `pin`
+    (default: when a GPU is there; pass False inside DataLoader workers) -- and a numpy view of its first 16 n bytes as
+    IMAGE_DESC records, offsets counted from the buffer's first byte.  pads[i] unused bytes go in front of image i."""
+    n = len(images)
+    if n == 0:
+        raise ValueError('pack_u8: no images')
+    arrays = [None if im is None else _u8_hwc(im) for im in images]
+    pads = [0] * n if pads is None else [int(p) for p in pads]
+    pos, offsets = IMAGE_DESC.itemsize * n, []
+    for a, pad in zip(arrays, pads):
+        pos += pad
+        offsets.append(pos)
+        pos += 0 if a is None else a.size
+    buffer = torch.empty(pos, dtype=torch.uint8, pin_memory=torch.cuda.is_available() if pin is None else bool(pin))
+    flat = buffer.numpy()
+    descs = flat[:IMAGE_DESC.itemsize * n].view(IMAGE_DESC)
+    end = IMAGE_DESC.itemsize * n
+    for i, (a, off) in enumerate(zip(arrays, offsets)):
+        flat[end:off] = 0
+        descs[i] = (off, 0, 0) if a is None else (off, a.shape[0], a.shape[1])
+        if a is not None:
+            flat[off:off + a.size] = a.reshape(-1)
+            end = off + a.size
+    return buffer, descs
+
+
+def image_descs(descs, nbytes):
+    """`descs` (IMAGE_DESC records, or their (n,4) int32 form, array or tensor) as a checked IMAGE_DESC array: every
+    image must lie inside a buffer of `nbytes` bytes -- the kernel reads where the table points."""
+    d = descs.numpy() if torch.is_tensor(descs) else np.asarray(descs)
+    if d.dtype != IMAGE_DESC:
+        if d.dtype != np.int32 or d.ndim != 2 or d.shape[1] != 4:
+            raise ValueError('descriptors: IMAGE_DESC records or an (n,4) int32 array')
+        d = np.ascontiguousarray(d).view(IMAGE_DESC)
+    d = np.ascontiguousarray(d.reshape(-1))
+    if d.size == 0:
+        raise ValueError('descriptors: empty table')
+    off, h, w = d['offset'], d['h'].astype(np.int64), d['w'].astype(np.int64)
+    absent = (h == 0) & (w == 0)
+    ok = absent | ((h > 0) & (w > 0) & (off >= 0) & (off + 3 * h * w <= nbytes))
+    if not ok.all():
+        raise ValueError('descriptor %d points outside the %d-byte buffer or has a bad size' % (int(np.argmin(ok)), nbytes))
+    return d
+
+
+def _resize_launch(dev_buffer, table_ptr, n, h, w, out=None):
+    """One t2o_resize_u8_to_f32 launch on the current stream: images in `dev_buffer`, n descriptors at device address table_ptr."""
+    dev = dev_buffer.device
+    if out is None:
+        out = torch.empty(n, 3, h, w, dtype=torch.float32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 3, h, w)):
+        raise ValueError('out must be a contiguous fp32 GPU tensor of shape %s' % ((n, 3, h, w),))
+    rc = _lib.load().t2o_resize_u8_to_f32(_ptr(dev_buffer), table_ptr, n, h, w, _ptr(out), _stream(dev))
+    _lib.check(rc, 't2o_resize_u8_to_f32')
+    return out
+
+
+def upload_packed(buffer, descs, device=None):
+    """The packed buffer on the device (ONE host-to-device copy; none if it is there already) and the device address of
+    its descriptor table: the buffer's head when pack_u8 laid it out, else a second, small upload of `descs`.
+    Returns (device buffer, table address, checked descriptors, keep-alive)."""
+    buffer = torch.from_numpy(buffer) if isinstance(buffer, np.ndarray) else buffer
+    if buffer.dtype != torch.uint8 or buffer.dim() != 1 or not buffer.is_contiguous():
+        raise ValueError('packed buffer must be a contiguous 1-D uint8 tensor')
+    descs = image_descs(descs, buffer.numel())
+    head = IMAGE_DESC.itemsize * descs.size
+    if device is None:
+        device = buffer.device if buffer.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    in_head = (not buffer.is_cuda and buffer.numel() >= head
+               and np.array_equal(buffer[:head].numpy().view(IMAGE_DESC), descs))
+    dev_buffer = buffer if buffer.is_cuda else buffer.to(device, non_blocking=True)
+    if in_head and dev_buffer.data_ptr() % 8 == 0:
+        return dev_buffer, dev_buffer.data_ptr(), descs, None
+    table = torch.from_numpy(descs.view(np.uint8)).to(dev_buffer.device, non_blocking=True)
+    return dev_buffer, table.data_ptr(), descs, table
+
+
+def resize_u8(images, size, device=None, out=None):
+    """The loaders' cv2.resize + transpose + / 255 (utils/visual_utils.py:6-31) for a batch of decoded images on the GPU:
+    (n,3,h,w) fp32 in [0,1], bit for bit data.resize_linear_u8(img, h, w).astype(float32).transpose(2,0,1) / 255.
+    images: a list of uint8 (H,W,3) arrays / CPU tensors of any sizes (None = absent: zeros), or an already packed
+    (buffer, descs) pair (pack_u8, data.collate_raw); size: int or (h, w).  One pinned buffer, one upload, one launch on
+    the current stream; nothing waits on the host."""
+    h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    if h <= 0 or w <= 0:
+        raise ValueError('resize_u8: size must be positive')
+    packed = isinstance(images, tuple) and len(images) == 2 and getattr(images[0], 'ndim', 0) == 1
+    buffer, descs = images if packed else pack_u8(images)
+    dev_buffer, table_ptr, descs, keep = upload_packed(buffer, descs, device)
+    return _resize_launch(dev_buffer, table_ptr, int(descs.size), h, w, out)
+
+
+def to_u8_hwc(t, out=None):
+    """(N,3,H,W) or (3,H,W) fp32 GPU tensor in [0,1] -> (N,H,W,3) uint8 GPU tensor = (t * 255) truncated, the rounding of
+    utils/visual_utils.py:50-58; equals (t * 255).permute(0,2,3,1).cpu().numpy().astype(uint8).  out: optional contiguous
+    uint8 GPU tensor of N H W 3 elements (any alignment)."""
+    _need_gpu(t)
+    t = t.detach()
+    t = t.reshape(-1, 3, *t.shape[-2:]) if t.dim() in (3, 4) and t.shape[-3] == 3 else None
+    if t is None:
+        raise ValueError('to_u8_hwc: expected (N,3,H,W) or (3,H,W)')
+    t = t.contiguous()
+    N, _, H, W = t.shape
+    if out is None:
+        out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=t.device)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == N * H * W * 3):
+        raise ValueError('out must be a contiguous uint8 GPU tensor of %d elements' % (N * H * W * 3))
+    rc = _lib.load().t2o_f32_to_u8_hwc(_ptr(t), N, H, W, _ptr(out), _stream(t.device))
+    _lib.check(rc, 't2o_f32_to_u8_hwc')
+    return out.view(N, H, W, 3)

@@ -22,7 +22,7 @@ import time
 import numpy as np
 import torch
 
-from .data import ACTIONS, FiveK
+from .data import ACTIONS, FiveK, collate_raw, device_batch
 
 OPERATIONS = [0, 1, 2, 3, 5, 6]                # gen_greedy_seqs_FiveK.py:39
 JPEG_QUALITY = 95                              # cv2.imwrite's default
@@ -30,7 +30,11 @@ JPEG_QUALITY = 95                              # cv2.imwrite's default
 
 def tensor2img(tensor):
     """(1,3,H,W) or (3,H,W) in [0,1] -> (H,W,3) uint8 RGB, rounded as utils/visual_utils.py:50-58 (that one returns BGR
-    for cv2.imwrite; PIL takes RGB)."""
+    for cv2.imwrite; PIL takes RGB).  A GPU tensor is converted there (functional.to_u8_hwc: the same product and
+    truncation), so the bytes cross the bus, not the floats."""
+    if tensor.is_cuda and tensor.dtype == torch.float32:
+        from . import functional as T
+        return T.to_u8_hwc(tensor.detach().reshape(1, 3, *tensor.shape[-2:]))[0].cpu().numpy()
     out = tensor.detach().reshape(3, *tensor.shape[-2:]).permute(1, 2, 0) * 255
     return out.cpu().numpy().astype(np.uint8)
 
@@ -74,13 +78,14 @@ def main(argv=None):
     ap.add_argument('--start', type=int, default=0, help='first item')
     ap.add_argument('--limit', type=int, default=None, help='number of items from --start on (default: to the end)')
     ap.add_argument('--overwrite', action='store_true', help='plan items again whose record exists')
+    ap.add_argument('--device_resize', action='store_true', help='resize the decoded pairs on the GPU (one launch per batch)')
     args = ap.parse_args(argv)
 
     from . import Executor, default_options, planner
     device = torch.device('cuda', torch.cuda.current_device())
     executor = Executor(default_options()).to(device)
     phase = 'train'
-    dataset = FiveK(args.img_dir, args.anno_dir, phase, args.session, args.img_size)
+    dataset = FiveK(args.img_dir, args.anno_dir, phase, args.session, args.img_size, raw=args.device_resize)
     stop = len(dataset) if args.limit is None else min(len(dataset), args.start + args.limit)
     todo = [i for i in range(args.start, stop) if args.overwrite or not os.path.exists(record_path(args.save_dir, phase, i))]
     written = 0
@@ -88,8 +93,12 @@ def main(argv=None):
         batch = todo[b0:b0 + args.pairs_per_batch]
         tik = time.time()
         items = [dataset[i] for i in batch]
-        inputs = [it[0].unsqueeze(0).to(device) for it in items]
-        targets = [it[1].unsqueeze(0).to(device) for it in items]
+        if args.device_resize:
+            img_x, img_y = device_batch(collate_raw(items), args.img_size, device)[:2]
+            inputs, targets = [img_x[k:k + 1] for k in range(len(items))], [img_y[k:k + 1] for k in range(len(items))]
+        else:
+            inputs = [it[0].unsqueeze(0).to(device) for it in items]
+            targets = [it[1].unsqueeze(0).to(device) for it in items]
         results = planner.beam_search_pairs(inputs, targets, None, executor, None, args.beam_size, OPERATIONS, ACTIONS,
                                             args.max_step, args.err, 'L1', replace=False)
         for i, it, img_x, img_y, (act_seqs, img_seqs) in zip(batch, items, inputs, targets, results):

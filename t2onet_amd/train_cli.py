@@ -23,7 +23,7 @@ from torch.utils.data import DataLoader, DistributedSampler
 from . import default_options
 from .actor import Actor
 from . import evaluate
-from .data import FiveK, FiveKAct, SyntheticFiveK
+from .data import DeviceBatches, FiveK, FiveKAct, SyntheticFiveK, collate_raw, device_batch
 from .train import Trainer
 
 
@@ -80,6 +80,8 @@ def main(argv=None):
     ap.add_argument('--word2vec', default=None, help='GloVe rows of the request vocabulary (.h5 of the reference, or .npy)')
     ap.add_argument('--val_items', type=int, default=64, help='synthetic runs: size of the validation split')
     ap.add_argument('--eager', action='store_true', help='no channels-last encoder / hipGraphs (debugging)')
+    ap.add_argument('--device_resize', action='store_true',
+                    help='real data: the loaders only decode; resize + layout run on the GPU, one launch per batch')
     args = ap.parse_args(argv)
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -104,18 +106,23 @@ def main(argv=None):
     trainer = Trainer(model, opt, graph_encoder=not args.eager)
     torch.manual_seed(args.manual_seed + 1000 * rank)        # independent sampling / dropout streams per rank
 
+    raw = args.device_resize and not args.synthetic
     dataset = SyntheticFiveK(n=args.batch_size * 64, size=args.img_size) if args.synthetic else \
-        FiveKAct(args.img_dir, args.anno_dir, args.act_dir, 'train', 1, args.img_size)
+        FiveKAct(args.img_dir, args.anno_dir, args.act_dir, 'train', 1, args.img_size, raw=raw)
     sampler = DistributedSampler(dataset, world, rank, shuffle=True) if world > 1 else None
+    raw_kw = dict(collate_fn=collate_raw, pin_memory=True) if raw else {}
     loader = DataLoader(dataset, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler,
-                        num_workers=args.num_workers, drop_last=True)
+                        num_workers=args.num_workers, drop_last=True, **raw_kw)
     if args.synthetic:
         val_loader = DataLoader(_EvalView(SyntheticFiveK(n=args.val_items, size=args.img_size, seed=args.manual_seed + 1)),
                                 batch_size=args.batch_size, shuffle=False, num_workers=args.num_workers)
     else:
         # the reference validates on FiveK(..., 'val'): no planned actions needed, full resolution (short side 600), one
         # image per batch (train_seq2seqL1.py:155-156) -- the validation L1 and checkpoint_best follow that
-        val_loader = DataLoader(FiveK(args.img_dir, args.anno_dir, 'val', 1), batch_size=1, shuffle=False, num_workers=1)
+        val_loader = DataLoader(FiveK(args.img_dir, args.anno_dir, 'val', 1, raw=raw), batch_size=1, shuffle=False, num_workers=1,
+                                **raw_kw)
+        if raw:
+            val_loader = DeviceBatches(val_loader, device=device, short_size=val_loader.dataset.short_size, images_only=True)
     ckpt_dir = os.path.join(args.run_dir, 'seq2seqL1_model')
     stats = {'train_iter': [], 'val_dist': [], 'best_val_dist': float('inf'), 'best_iter': 0}
     itr, epoch = 0, 0
@@ -124,9 +131,12 @@ def main(argv=None):
         epoch += 1
         if sampler is not None:
             sampler.set_epoch(epoch)
-        for img_x, img_y, x, y, gt_params, _ in loader:
+        for batch in loader:
             itr += 1
             tik = time.time()
+            if raw:                                                  # decoded bytes: one upload, one resize launch
+                batch = device_batch(batch, args.img_size, device, images_only=True)
+            img_x, img_y, x, y, gt_params, _ = batch
             lengths = (x != opt.null_id).sum(1)
             x, y, img_x, img_y, gt_params = (t.to(device, non_blocking=True) for t in (x, y, img_x, img_y, gt_params))
             if itr % 2 == 1:
