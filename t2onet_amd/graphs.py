@@ -187,9 +187,10 @@ class GraphedEpisodeStep:
     length), the step kernels of functional.lstm_layer, forked onto a second stream inside the capture (Actor._encode_request), i.e. a parallel branch of the
     graph beside the first image-encoder pass and, in the backward, beside the last one.
 
-    The graph zeroes the flat gradient buffer first.  Sampling (`torch.rand` in actor.sample_categorical) and the
-    request encoder's dropout use the generator's graph-safe state: every replay draws fresh numbers.  One instance
-    per (image shape, request length L, reinforce_sample)."""
+    The graph zeroes the flat gradient buffer first.  Sampling (functional.choose_op, fed by the one `torch.rand` per
+    episode of Actor.episode_decode) and the request encoder's dropout use the generator's graph-safe state: every replay
+    draws fresh numbers.  `ops` is the captured (B, decoder_max_len) tensor of chosen operator ids: each replay overwrites
+    it, so it holds what the last replay drew.  One instance per (image shape, request length L, reinforce_sample)."""
 
     def __init__(self, trainer, x, lengths, longest, img, target, reinforce_sample, warmup=2):
         model = trainer.model
@@ -238,6 +239,7 @@ class GraphedEpisodeStep:
             self._keep = (tr.__dict__.get('_tape_obj'), tr._trunk.__dict__.get('arena') if tr._trunk is not None else None)
             lengths = (self.s_x != tr.opt.null_id).sum(1)     # on the device, inside the graph: no host-side lengths to copy
             _, imgs, ops, _ = model.episode_forward(self.s_x, self.s_img, None, self.reinforce_sample, lengths, self.longest, stack=False)
+            self.ops = ops
             loss = end_l1_loss(imgs, ops, tr.opt.end_id, self.s_target)
             loss.backward()
             tr._flush_tape()                                   # the decoder's weight gradients: one product per weight, in the graph
