@@ -721,6 +721,30 @@ int t2o_resize_u8_to_f32(const unsigned char* src, const t2o_image_desc_t* descs
                          void* stream);
 int t2o_f32_to_u8_hwc(const float* img, int n, int h, int w, unsigned char* out, void* stream);
 
+/* ---- a known operator list replayed on 8-bit pictures at their native size, 8-bit in and 8-bit out (t2o_replay.hip):
+ * what an edit's decision, taken on a bounded proxy, costs on the original photo.  Job j reads the (h,w,3) uint8 RGB
+ * picture at src + src_offset (any byte alignment; several jobs may name the same source) and writes (h,w,3) uint8 at
+ * out + out_offset.  Per pixel x = byte / 255 (the conversion of t2o_resize_u8_to_f32 for a source of the output's size);
+ * for k < steps: x = clamp(process(ops[k], x, params[j][k]), 0, 1), Operator.execute with specified_param and no mask
+ * (models/operators.py:112-131), ops[k] = -1 being the identity; byte = x * 255 truncated, as t2o_f32_to_u8_hwc.  The
+ * bytes are those of that materialised path (resize at the picture's size, t2o_op_fwd per step, f32_to_u8_hwc): the same
+ * device functions run, at 6 bytes of global traffic per pixel.  steps = 0 is the two conversions back to back.
+ * Operators 0, 1, 2, 3, 5, 6, 7 and -1; the sharpness zero-pads the INTERMEDIATE image at the picture's border.
+ * jobs: HOST array of J <= 64 (copied into the kernel arguments); params: DEVICE (J, 8, 24) fp32, may be NULL when no
+ * job applies an operator.  One launch for all jobs; no allocation, no host synchronisation, capturable, deterministic.
+ * The caller guarantees that the offsets and sizes lie inside src / out.
+ * T2O_EUNSUPPORTED: operator 4, or more than one sharpness among a job's steps (the actor's op mask forbids repeats,
+ * models/actor.py:235-236; one sharpness keeps the halo at one pixel).  T2O_EINVAL: J outside 1..64, steps outside
+ * 0..8, any other operator index, null pointers, non-positive sizes, negative offsets. */
+typedef struct {
+  long long src_offset, out_offset;   /* first byte of the source / destination picture, counted from src / out */
+  int h, w;
+  int steps;                          /* operators applied: ops[0 .. steps) */
+  int ops[8];
+} t2o_replay_job_t;
+int t2o_replay_u8(const unsigned char* src, unsigned char* out, const t2o_replay_job_t* jobs, int J, const float* params,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1857,3 +1857,64 @@ def to_u8_hwc(t, out=None):
     rc = _lib.load().t2o_f32_to_u8_hwc(_ptr(t), N, H, W, _ptr(out), _stream(t.device))
     _lib.check(rc, 't2o_f32_to_u8_hwc')
     return out.view(N, H, W, 3)
+
+
+# ---- 8-bit replay (t2o_replay.hip): a known operator list on uint8 pictures at their native size ----
+
+REPLAY_MAX_JOBS, REPLAY_MAX_STEPS = 64, 8
+
+
+class ReplayJob(ctypes.Structure):
+    """t2o_replay_job_t of include/t2onet_hip.h (field for field)."""
+    _fields_ = [('src_offset', ctypes.c_longlong), ('out_offset', ctypes.c_longlong), ('h', ctypes.c_int), ('w', ctypes.c_int),
+                ('steps', ctypes.c_int), ('ops', ctypes.c_int * REPLAY_MAX_STEPS)]
+
+
+def replay_jobs(jobs):
+    """jobs: a sequence of (src_offset, out_offset, h, w, ops) with ops a list of executor indices (-1 = identity) ->
+    the ctypes array t2o_replay_u8 takes.  `steps` is len(ops) even beyond 8, so that the library is the one to refuse it."""
+    arr = (ReplayJob * len(jobs))()
+    for c, (src_offset, out_offset, h, w, ops) in zip(arr, jobs):
+        c.src_offset, c.out_offset, c.h, c.w, c.steps = int(src_offset), int(out_offset), int(h), int(w), len(ops)
+        for k, op in enumerate(list(ops)[:REPLAY_MAX_STEPS]):
+            c.ops[k] = int(op)
+    return arr
+
+
+def replay_status(rc, what='t2o_replay_u8'):
+    """The library's status as an exception carrying its text: invalid argument -> ValueError, unsupported operator list ->
+    NotImplementedError, anything else -> RuntimeError."""
+    if rc == 0:
+        return
+    msg = '%s failed (status %d): %s' % (what, rc, _lib.load().t2o_last_error().decode('utf-8', 'replace'))
+    raise {1: ValueError, 2: NotImplementedError}.get(rc, RuntimeError)(msg)
+
+
+def replay_u8(src_u8, jobs, params, out=None):
+    """Apply known (operator, parameter) lists to uint8 (h,w,3) RGB pictures at their native size, bytes in and bytes out,
+    in ONE launch (t2o_replay_u8): job j = (src_offset, out_offset, h, w, ops) reads its picture at byte src_offset of the
+    1-D uint8 GPU tensor src_u8 (any alignment; jobs may share a source), applies ops[k] with params[j, k] ((J,8,24) fp32
+    GPU; None when no job applies an operator) as Operator.execute does with specified_param, and writes at byte out_offset of
+    `out` (allocated to fit when None).  The bytes equal resize_u8 at the picture's size -> operator_apply per step ->
+    to_u8_hwc.  Returns out (1-D uint8)."""
+    if not (torch.is_tensor(src_u8) and src_u8.is_cuda and src_u8.dtype == torch.uint8 and src_u8.is_contiguous()):
+        raise ValueError('replay_u8: src must be a contiguous uint8 GPU tensor')
+    jobs = [tuple(j) for j in jobs]
+    for j, (so, oo, h, w, ops) in enumerate(jobs):
+        if h > 0 and w > 0 and not (0 <= so and so + 3 * h * w <= src_u8.numel()):
+            raise ValueError('replay_u8: job %d reads outside the %d-byte source' % (j, src_u8.numel()))
+    need = max([oo + 3 * h * w for _, oo, h, w, _ in jobs if h > 0 and w > 0] or [1])
+    if out is None:
+        out = torch.empty(need, dtype=torch.uint8, device=src_u8.device)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == src_u8.device):
+        raise ValueError('replay_u8: out must be a contiguous uint8 GPU tensor on the source\'s device')
+    elif out.numel() < need or any(oo < 0 for _, oo, _, _, _ in jobs):
+        raise ValueError('replay_u8: a job writes outside the %d-byte output' % out.numel())
+    if params is not None:
+        _need_gpu(params)
+        params = params.contiguous()
+        if tuple(params.shape) != (len(jobs), REPLAY_MAX_STEPS, PARAM_PAD):
+            raise ValueError('replay_u8: params must be (J, 8, 24), got %s' % (tuple(params.shape),))
+    rc = _lib.load().t2o_replay_u8(_ptr(src_u8), _ptr(out), replay_jobs(jobs), len(jobs), _ptr(params), _stream(src_u8.device))
+    replay_status(rc)
+    return out
