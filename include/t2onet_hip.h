@@ -745,6 +745,32 @@ typedef struct {
 int t2o_replay_u8(const unsigned char* src, unsigned char* out, const t2o_replay_job_t* jobs, int J, const float* params,
                   void* stream);
 
+/* ---- the metrics of the test loop in one call: utils/eval.py:50-60 (ImageEvaluator.update: input / output L1 and SSIM),
+ * utils/ssim/__init__.py:20-40 (the SSIM itself) and test_seq2seqL1.py:60-74 (the END-image select and the two L1
+ * distances the loop averages).  imgs: HOST array of 1 <= T <= 8 device pointers to (B,C,H,W) step images, first: device
+ * int64 (B) -- the conventions of t2o_end_select_l1_fwd; the output image of sample b is imgs[first[b]][b], read where it
+ * lies (a first[b] outside [0,T) counts as T-1).  out4 (device, usually a row of a caller-owned table):
+ *   out4[0] = mean |input - target|     out4[2] = SSIM(input, target)
+ *   out4[1] = mean |out - target|       out4[3] = SSIM(out, target)
+ * the SSIM values being the reference's size_average=True value (the mean of t2o_ssim_fwd's per-sample means); with
+ * with_ssim == 0 slots 2 and 3 are written as 0 and no Gaussian pass runs.  Two launches: one workgroup per 32 x 32 tile
+ * of a plane reads the three images once (with halo) and writes four partials; a finalize adds them in a fixed order.
+ * Deterministic, no float atomics.  workspace: t2o_eval_metrics_workspace_bytes(B,C,H,W). */
+size_t t2o_eval_metrics_workspace_bytes(int B, int C, int H, int W);
+int t2o_eval_metrics(const float* input, const float* const* imgs, int T, const long long* first,
+                     const float* target, float* out4, int with_ssim,
+                     void* workspace, size_t workspace_bytes, int B, int C, int H, int W, void* stream);
+
+/* ---- torch.var(torch.cat(ends), dim=0).mean() of test_variance (test_seq2seqL1.py:130-133) from the step images ----
+ * imgs: HOST array of R*T device pointers, request r's step t = imgs[r*T+t], (B,row) floats; first: HOST array of R
+ * device pointers to int64 (B).  R <= 16, T <= 8, N = R*B >= 2.  For element p of a row the samples are the N values
+ * imgs[r*T+first[r][b]][b*row+p]; their unbiased variance is taken in two passes (mean, then squared deviations over
+ * N-1) and out[0] = the mean over the row's elements.  Two launches, deterministic; row is any positive size.
+ * workspace: t2o_end_select_var_mean_workspace_bytes(row). */
+size_t t2o_end_select_var_mean_workspace_bytes(size_t row);
+int t2o_end_select_var_mean(const float* const* imgs, const long long* const* first, int R, int T, int B,
+                            size_t row, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

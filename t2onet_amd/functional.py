@@ -57,12 +57,9 @@ def _mask(mask, img):
 _ws_need = {}
 
 
-def workspace(B, H, W, device):
-    """Per-(device, stream) scratch, grown on demand; kernels on one stream run in order, so one buffer
-    per stream is enough."""
-    need = _ws_need.get((B, H, W))
-    if need is None:
-        need = _ws_need[(B, H, W)] = _lib.load().t2o_workspace_bytes(B, H, W)
+def _scratch(need, device):
+    """Per-(device, stream) scratch of at least `need` bytes, grown on demand; kernels on one stream run in order, so one
+    buffer per stream is enough."""
     if torch.cuda.is_current_stream_capturing():
         # inside a hipGraph capture the buffer's address is baked into the graph: a private allocation from the graph's
         # pool (a cached buffer could be replaced -- freed -- by a later, larger request on the same stream)
@@ -73,6 +70,14 @@ def workspace(B, H, W, device):
         ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=device)
         _workspaces[key] = ws
     return ws
+
+
+def workspace(B, H, W, device):
+    """The scratch of the operator / loss kernels for images of this shape (t2o_workspace_bytes)."""
+    need = _ws_need.get((B, H, W))
+    if need is None:
+        need = _ws_need[(B, H, W)] = _lib.load().t2o_workspace_bytes(B, H, W)
+    return _scratch(need, device)
 
 
 class _OperatorFn(torch.autograd.Function):
@@ -1052,6 +1057,75 @@ def ssim(img1, img2, size_average=True):
         raise ValueError('ssim expects fp32 images')
     out = _SsimFn.apply(img1.contiguous(), img2.contiguous())
     return out.mean() if size_average else out
+
+
+def _first_steps(first, B, device, what):
+    if not (torch.is_tensor(first) and first.is_cuda and first.dtype == torch.int64 and tuple(first.shape) == (B,)):
+        raise ValueError('%s: first must be an int64 GPU tensor of shape (%d,)' % (what, B))
+    if first.device != device:
+        raise ValueError('%s: tensors on different devices' % what)
+    return first.contiguous()
+
+
+def eval_metrics(input, imgs, first, target, out=None, with_ssim=True):
+    """The four numbers the test loop takes per batch (utils/eval.py:50-60, test_seq2seqL1.py:60-74) in ONE call
+    (t2o_eval_metrics): [mean |input - target|, mean |out - target|, SSIM(input, target), SSIM(out, target)] with
+    out[b] = imgs[first[b]][b] -- imgs the list of T <= 8 (B,C,H,W) step images of an episode (episode_forward(...,
+    stack=False)), first (B) int64 on the GPU (train.first_end_step), read where the images lie.  with_ssim=False: the two
+    SSIM slots are 0 and no Gaussian pass runs.  out: a contiguous fp32 GPU tensor of 4 elements to fill (a row of a table);
+    a new (4,) tensor otherwise.  No host synchronisation."""
+    imgs = list(imgs)
+    _need_gpu(input, target, out, *imgs)
+    if target.dim() != 4 or input.shape != target.shape or any(t.shape != target.shape for t in imgs):
+        raise ValueError('eval_metrics: input, target and every step image must be (B,C,H,W) tensors of one shape')
+    B, C, H, W = target.shape
+    dev = target.device
+    first = _first_steps(first, B, dev, 'eval_metrics')
+    if out is None:
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+    elif not (out.is_contiguous() and out.numel() == 4):
+        raise ValueError('eval_metrics: out must be a contiguous fp32 GPU tensor of 4 elements')
+    if any(t.device != dev for t in [input, out] + imgs):
+        raise ValueError('eval_metrics: tensors on different devices')
+    input, target = input.detach().contiguous(), target.detach().contiguous()
+    imgs = [t.detach().contiguous() for t in imgs]
+    lib = _lib.load()
+    ws = _scratch(lib.t2o_eval_metrics_workspace_bytes(B, C, H, W), dev)
+    rc = lib.t2o_eval_metrics(_ptr(input), _ptr_array(imgs), len(imgs), _ptr(first), _ptr(target), _ptr(out), 1 if with_ssim else 0,
+                              _ptr(ws), ws.numel(), B, C, H, W, _stream(dev))
+    _lib.check(rc, 't2o_eval_metrics')
+    return out
+
+
+def end_select_var_mean(lists, firsts, out=None):
+    """torch.var(torch.cat(ends), dim=0).mean() of test_variance (test_seq2seqL1.py:130-133) in ONE call
+    (t2o_end_select_var_mean): lists = R <= 16 lists of T <= 8 step images (B, ...) -- one episode per request on the same
+    batch -- firsts = R (B) int64 GPU tensors; ends[r][b] = lists[r][firsts[r][b]][b] is read where it lies.  out: a
+    contiguous fp32 GPU tensor of 1 element to fill (an entry of a table); a new 0-d tensor otherwise.  No host
+    synchronisation."""
+    lists = [list(l) for l in lists]
+    firsts = list(firsts)
+    flat = [t for l in lists for t in l]
+    _need_gpu(out, *flat)
+    if not flat or len(firsts) != len(lists) or any(len(l) != len(lists[0]) for l in lists):
+        raise ValueError('end_select_var_mean: R lists of T step images each and R first-step tensors')
+    shape, dev = flat[0].shape, flat[0].device
+    if len(shape) < 1 or any(t.shape != shape or t.device != dev for t in flat):
+        raise ValueError('end_select_var_mean: every step image must have one shape (B, ...) and one device')
+    B = shape[0]
+    row = flat[0].numel() // max(B, 1)
+    firsts = [_first_steps(f, B, dev, 'end_select_var_mean') for f in firsts]
+    if out is None:
+        out = torch.empty((), dtype=torch.float32, device=dev)
+    elif not (out.is_contiguous() and out.numel() == 1 and out.device == dev):
+        raise ValueError('end_select_var_mean: out must be a contiguous fp32 GPU tensor of 1 element on the images\' device')
+    flat = [t.detach().contiguous() for t in flat]
+    lib = _lib.load()
+    ws = _scratch(lib.t2o_end_select_var_mean_workspace_bytes(row), dev)
+    rc = lib.t2o_end_select_var_mean(_ptr_array(flat), _ptr_array(firsts), len(lists), len(lists[0]), B, row, _ptr(out), _ptr(ws),
+                                     ws.numel(), _stream(dev))
+    _lib.check(rc, 't2o_end_select_var_mean')
+    return out
 
 
 def candidates_l1(op, img, target, params):

@@ -1,6 +1,6 @@
 """Training driver with the reference's loop structure (experiments/t2onet/train_seq2seqL1.py:22-176):
 alternating supervised / episode steps, running-mean timers ('fs time', 'L1 time'), and every
-`checkpoint_every` iterations: evaluation on the validation split (evaluate.test), a `model.pth` checkpoint with
+`checkpoint_every` iterations: evaluation on the validation split (evaluate.test; --device_eval: evaluate.test_on_device), a `model.pth` checkpoint with
 the reference's state_dict layout, and `checkpoint_best` when the validation L1 improved (:103-131).
 The request encoder's word rows come from the GloVe table (--word2vec, the reference's
 {dataset}_vocabs_glove_feat_{session}.h5 or the same matrix as .npy); without one the loop refuses to freeze random
@@ -82,6 +82,8 @@ def main(argv=None):
     ap.add_argument('--eager', action='store_true', help='no channels-last encoder / hipGraphs (debugging)')
     ap.add_argument('--device_resize', action='store_true',
                     help='real data: the loaders only decode; resize + layout run on the GPU, one launch per batch')
+    ap.add_argument('--device_eval', action='store_true',
+                    help='validation through evaluate.test_on_device: one fused metrics launch per image, one host read per pass')
     args = ap.parse_args(argv)
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -158,7 +160,8 @@ def main(argv=None):
             if itr % args.checkpoint_every == 0 or itr >= args.num_iters:
                 sync_batchnorm_buffers(model, world)                  # every rank takes part in the collective
                 if rank == 0:
-                    init_val_dist, val_dist = evaluate.test(model, val_loader, opt, device=device, verbose=False)
+                    validate = evaluate.test_on_device if args.device_eval else evaluate.test
+                    init_val_dist, val_dist = validate(model, val_loader, opt, device=device, verbose=False)[:2]
                     model.train()
                     print('validation L1 dist {:.4f} (init {:.4f})'.format(val_dist, init_val_dist), flush=True)
                     stats['val_dist'].append(val_dist)
