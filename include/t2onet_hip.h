@@ -745,6 +745,31 @@ typedef struct {
 int t2o_replay_u8(const unsigned char* src, unsigned char* out, const t2o_replay_job_t* jobs, int J, const float* params,
                   void* stream);
 
+/* ---- the same replay with Operator.execute's MASK operand (t2o_replay_mask.hip): a local edit at native size.  Step k
+ * of job j may name one of n_masks <= 4 uint8 (h,w) planes of the job's own size, plane i starting at masks +
+ * mask_offsets[i] (any byte alignment; the jobs of a call share the planes): mask_of[8 j + k] is its index, or -1.  Per
+ * pixel x = byte / 255; for k < steps, with o = process(ops[k], x, params[j][k]):
+ *   x = clamp(o * m + x * (1 - m), 0, 1), m = maskbyte / 255      where the step names a mask
+ *   x = clamp(o, 0, 1)                                            where it names none
+ * (models/operators.py:112-131; 0 leaves the pixel, 255 applies the operator, values between feather the edge); byte =
+ * x * 255 truncated.  A masked sharpness blends the stencil's result with the stencil's input at the centre pixel, and a
+ * masked step in front of a sharpness is blended on the ring as well; the zero padding of the intermediate image at the
+ * picture's border is t2o_replay_u8's.  The bytes are those of the materialised path (resize at the picture's size,
+ * t2o_op_fwd per step with the mask as (1,1,h,w) fp32 = byte / 255, f32_to_u8_hwc): the same device functions run, at
+ * 6 bytes of global traffic per pixel plus 1 per distinct mask the job's list names.  A workgroup skips a step whose
+ * mask is 0 on its whole 32 x 32 window (the bytes are the same: o * 0 + x * 1 = x), so a small region costs little on
+ * a large photo.  An index on an identity step (-1) or beyond `steps` is ignored.
+ * jobs, mask_of ((J, 8) ints), mask_offsets: HOST arrays, copied into the kernel arguments; params, masks: DEVICE.
+ * masks / mask_offsets may be NULL when n_masks = 0.  One launch; no allocation, no host synchronisation, capturable,
+ * deterministic.  The caller guarantees that offsets and sizes lie inside src / out / masks.
+ * Status codes as t2o_replay_u8 (operator 4 and a second sharpness: T2O_EUNSUPPORTED); T2O_EINVAL also for n_masks
+ * outside 0..4, a mask index outside -1..n_masks-1 among a job's steps, a negative mask offset.
+ * Measured on one synthetic 4000 x 6000 picture only (profiles/replay_u8_masked.txt); not measured: real photos through
+ * the decoder, masks larger than the L2 working set as a case of their own, the kernel's share of peak. */
+int t2o_replay_u8_masked(const unsigned char* src, unsigned char* out, const t2o_replay_job_t* jobs, const int* mask_of, int J,
+                         const float* params, const unsigned char* masks, const long long* mask_offsets, int n_masks,
+                         void* stream);
+
 /* ---- the metrics of the test loop in one call: utils/eval.py:50-60 (ImageEvaluator.update: input / output L1 and SSIM),
  * utils/ssim/__init__.py:20-40 (the SSIM itself) and test_seq2seqL1.py:60-74 (the END-image select and the two L1
  * distances the loop averages).  imgs: HOST array of 1 <= T <= 8 device pointers to (B,C,H,W) step images, first: device

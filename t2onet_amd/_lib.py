@@ -155,6 +155,7 @@ SIGNATURES = {
     't2o_resize_u8_to_f32': (_I, [_P, _P, _I, _I, _I, _P, _P]),
     't2o_f32_to_u8_hwc': (_I, [_P, _I, _I, _I, _P, _P]),
     't2o_replay_u8': (_I, [_P, _P, _P, _I, _P, _P]),
+    't2o_replay_u8_masked': (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
     't2o_eval_metrics_workspace_bytes': (_Z, [_I, _I, _I, _I]),
     't2o_eval_metrics': (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _Z, _I, _I, _I, _I, _P]),
     't2o_end_select_var_mean_workspace_bytes': (_Z, [_Z]),

@@ -3,9 +3,11 @@ real photo needs it: the DECISION -- which operators, with which parameters -- i
 (the short-side-600 size the test loader uses, utils/visual_utils.py:34-47), and the decision is then APPLIED to the
 original bytes at their native size by the fused 8-bit replay kernel (functional.replay_u8: 6 bytes of memory traffic
 per pixel, no fp32 image of the photo ever exists)."""
+import numpy as np
 import torch
 
 from . import functional as T
+from .actor import OP_MASK
 from .data import short_side_size, txt2idx
 
 
@@ -21,7 +23,63 @@ def first_end(ops_vocab, end_id):
     return ops_vocab.index(end_id) if end_id in ops_vocab else len(ops_vocab)
 
 
-def edit_image(model, img_u8_hwc, x, proxy_short=600):
+def nearest_index(src, dst):
+    """Source index of each of `dst` destination samples along an axis of `src`: OpenCV's published INTER_NEAREST rule
+    sx = min(floor(x * src / dst), src - 1) with the scale src / dst in double -- what the reference's
+    resize_and_union_mask applies to a mask (cv2.INTER_NEAREST).  Returns an int64 array of length dst."""
+    scale = np.float64(src) / np.float64(dst)
+    return np.minimum(np.floor(np.arange(dst, dtype=np.float64) * scale).astype(np.int64), src - 1)
+
+
+def _checked_masks(masks, h, w):
+    """masks {executor operator index or 'all': uint8 (h, w)} -> ([distinct planes], {operator index: plane number}).
+    'all' stands for every operator the actor can choose (actor.OP_MASK); an entry for one operator wins over it; planes
+    that are the same object are uploaded once."""
+    planes, slot_of, by_op = [], {}, {}
+    for key in sorted(masks, key=lambda k: (k != 'all', str(k))):              # 'all' first, so that named entries overwrite it
+        a = masks[key].numpy() if torch.is_tensor(masks[key]) else np.asarray(masks[key])
+        if a.dtype != np.uint8 or a.shape != (h, w):
+            raise ValueError('edit_image: mask %r must be uint8 (%d, %d), the photo\'s size; got %s %s' % (key, h, w, a.dtype, a.shape))
+        if id(masks[key]) not in slot_of:
+            slot_of[id(masks[key])] = len(planes)
+            planes.append(np.ascontiguousarray(a))
+        if key == 'all':
+            targets = [i - 3 for i, allowed in enumerate(OP_MASK) if allowed and i >= 3]
+        elif isinstance(key, (int, np.integer)) and 0 <= int(key) < len(T.OP_NPARAM):
+            targets = [int(key)]
+        else:
+            raise ValueError('edit_image: mask key %r is neither \'all\' nor an executor operator index 0..7' % (key,))
+        for op in targets:
+            by_op[op] = slot_of[id(masks[key])]
+    if len(planes) > T.REPLAY_MAX_MASKS:
+        raise ValueError('edit_image: %d distinct masks, the replay takes %d' % (len(planes), T.REPLAY_MAX_MASKS))
+    return planes, by_op
+
+
+def _append_planes(buffer, planes):
+    """The packed photo with the mask planes behind it, so that ONE upload carries both (a plane is 1 byte per pixel: raw
+    bytes outside the descriptor table) -> (buffer, byte offset of each plane)."""
+    whole = torch.empty(buffer.numel() + sum(p.size for p in planes), dtype=torch.uint8, pin_memory=buffer.is_pinned())
+    whole[:buffer.numel()] = buffer
+    flat, pos, offsets = whole.numpy(), buffer.numel(), []
+    for p in planes:
+        offsets.append(pos)
+        flat[pos:pos + p.size] = p.reshape(-1)
+        pos += p.size
+    return whole, offsets
+
+
+def _proxy_mask_dict(dev_buffer, mask_offsets, by_op, size, proxy_size):
+    """What Actor.get_gt_mask reads, [{str(vocabulary id): [(1, ph, pw) fp32 mask]}], from the native planes on the device:
+    nearest_index along both axes (cv2.INTER_NEAREST of resize_and_union_mask), byte / 255."""
+    (h, w), (ph, pw) = size, proxy_size
+    iy = torch.from_numpy(nearest_index(h, ph)).to(dev_buffer.device)
+    ix = torch.from_numpy(nearest_index(w, pw)).to(dev_buffer.device)
+    proxies = [(dev_buffer[off:off + h * w].view(h, w)[iy][:, ix].to(torch.float32) / 255.0).unsqueeze(0) for off in mask_offsets]
+    return [{str(op + 3): [proxies[slot]] for op, slot in by_op.items()}]
+
+
+def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None):
     """img_u8_hwc: the decoded photo, uint8 (h,w,3) RGB (array or CPU tensor); x: (1, L) request token ids.
     Returns (steps_u8, ops, params):
       steps_u8  (max(n,1), h, w, 3) uint8 GPU tensor: picture k is the photo after the first k+1 of the n chosen operators,
@@ -30,22 +88,33 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600):
       params    (n, 24) fp32 GPU tensor, their parameter rows.
     The photo is uploaded once; the proxy is made on the device only when the short side exceeds proxy_short (no
     upscaling: a smaller photo is its own proxy); the arg-max episode runs in eval mode under no_grad; pred_ops is read
-    back once; ONE replay_u8 launch writes every prefix of the list at native size."""
+    back once; ONE replay_u8 launch writes every prefix of the list at native size.
+    masks: None (a global edit), or {executor operator index or 'all': uint8 (h, w) array at the photo's NATIVE size} for
+    a local edit -- 0 leaves a pixel, 255 applies the operator, values between feather the edge; 'all' stands for every
+    operator the actor can choose, an entry for one operator wins over it.  The planes travel behind the photo in the same
+    upload; the proxy sees each one through nearest_index (indexed on the device, / 255) as the mask_dict of
+    Actor.get_gt_mask (one host read of the chosen operator per step, as the reference); ONE replay_u8_masked launch then
+    writes every prefix at native size under the native planes."""
     img = T._u8_hwc(img_u8_hwc)
     h, w = img.shape[:2]
     dev = next(model.parameters()).device
     opt = model.opt
+    planes, by_op = _checked_masks(masks, h, w) if masks is not None else ([], {})
     buffer, descs = T.pack_u8([img])
+    mask_offsets = []
+    if masks is not None:
+        buffer, mask_offsets = _append_planes(buffer, planes)
     dev_buffer, table_ptr, descs, _keep = T.upload_packed(buffer, descs, dev)
     ph, pw = short_side_size(h, w, proxy_short) if min(h, w) > proxy_short else (h, w)
     proxy = T._resize_launch(dev_buffer, table_ptr, 1, ph, pw)
+    mask_dict = None if masks is None else _proxy_mask_dict(dev_buffer, mask_offsets, by_op, (h, w), (ph, pw))
     x = torch.as_tensor(x, dtype=torch.long).view(1, -1)
     lengths = (x != opt.null_id).sum(1)                      # on the host, before the copy
     was_training = model.training
     model.eval()
     try:
         with torch.no_grad():
-            _, _, pred_ops, pred_params = model.episode_forward(x.to(dev), proxy, None, reinforce_sample=False, lengths=lengths)
+            _, _, pred_ops, pred_params = model.episode_forward(x.to(dev), proxy, mask_dict, reinforce_sample=False, lengths=lengths)
     finally:
         model.train(was_training)
     ops_vocab = pred_ops[0].cpu().tolist()                   # the one host read: the operator names are wanted anyway
@@ -59,5 +128,9 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600):
     jobs = [(src_offset, j * nbytes, h, w, ops[:j + 1]) for j in range(J)]       # n = 0: one job with no step
     table = torch.zeros(J, T.REPLAY_MAX_STEPS, T.PARAM_PAD, device=dev)
     table[:, :n] = params
-    out = T.replay_u8(dev_buffer, jobs, table)
+    if masks is None:
+        out = T.replay_u8(dev_buffer, jobs, table)
+    else:
+        mask_of = [by_op.get(op, -1) for op in ops]
+        out = T.replay_u8_masked(dev_buffer, [job + (mask_of[:j + 1],) for j, job in enumerate(jobs)], table, dev_buffer, mask_offsets)
     return out[:J * nbytes].view(J, h, w, 3), ops, params

@@ -7,6 +7,11 @@ pictures after each operator as {k}_inference_<name>.<ext> (k = 1 ..), and <name
 'operations': [(operator name, its parameters), ...]}] under the reference's operator names and parameter counts
 (demo/seq2seqL1.py:121-122,193-196).  Images are written with PIL, the format chosen by the extension.
 
+--mask [NAME=]FILE (repeatable) makes it a LOCAL edit: FILE is decoded as 8-bit grey and must have the photo's size; 0
+leaves a pixel as it is, 255 applies the operator, values between feather the edge.  NAME is one of the operator names
+above and binds the mask to that operator; without a name the mask applies to every operator (a named mask wins).  At
+most 4 distinct files.  The record then also holds 'masks': {name or 'all': file}.
+
 The actor decides on a proxy of the photo (short side --proxy_short, the test loader's 600; a smaller photo is its own
 proxy) and the decision is applied to the photo at its native size by the fused 8-bit replay kernel (edit.edit_image).
 
@@ -35,8 +40,47 @@ def operations_record(ops, params):
     return [(ACTIONS[op], [float(v) for v in row[:ACT2PN[ACTIONS[op]]]]) for op, row in zip(ops, rows)]
 
 
-def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, multi_img=False):
-    """The files of one edit (see the module docstring); steps_u8: (max(n,1), h, w, 3) uint8 array.  Returns the record."""
+def parse_mask_args(specs):
+    """--mask values ([NAME=]FILE) -> {operator name or 'all': file}.  NAME must be one of ACTIONS; what stands in front
+    of the first '=' counts as a name unless it looks like part of a path (holds a separator or a dot).  At most 4
+    distinct files.  Raises ValueError."""
+    named = {}
+    for spec in specs or []:
+        head, sep, tail = spec.partition('=')
+        if sep and head in ACTIONS:
+            name, path = head, tail
+        elif sep and not (os.sep in head or '/' in head or '.' in head):
+            raise ValueError('--mask %s: %r is not an operator name (one of %s)' % (spec, head, ', '.join(ACTIONS)))
+        else:
+            name, path = 'all', spec
+        if not path:
+            raise ValueError('--mask %s: no file given' % spec)
+        named[name] = path
+    if len(set(named.values())) > 4:
+        raise ValueError('--mask: %d distinct mask files, at most 4 are taken' % len(set(named.values())))
+    return named
+
+
+def load_masks(named, h, w):
+    """{name: file} -> the `masks` argument of edit.edit_image: every file decoded with PIL as 8-bit grey, one array per
+    distinct file; a size other than the photo's (h, w) is an error naming both."""
+    from PIL import Image
+    import numpy as np
+    by_file, masks = {}, {}
+    for name, path in named.items():
+        if path not in by_file:
+            with Image.open(path) as im:
+                a = np.ascontiguousarray(np.asarray(im.convert('L'), dtype=np.uint8))
+            if a.shape != (h, w):
+                raise ValueError('--mask %s is %d x %d (width x height), the photo is %d x %d' % (path, a.shape[1], a.shape[0], w, h))
+            by_file[path] = a
+        masks['all' if name == 'all' else ACTIONS.index(name)] = by_file[path]
+    return masks
+
+
+def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, multi_img=False, masks=None):
+    """The files of one edit (see the module docstring); steps_u8: (max(n,1), h, w, 3) uint8 array; masks: {name: file}
+    of a local edit, recorded when given.  Returns the record."""
     from PIL import Image
     name, ext = os.path.splitext(os.path.basename(img_path))
     out_dir = os.path.join(save_dir, name)
@@ -48,6 +92,8 @@ def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, mu
         for k in range(len(ops)):
             Image.fromarray(steps_u8[k]).save(os.path.join(out_dir, '%d_inference_%s%s' % (k + 1, name, ext)))
     info = {'input': input_name, 'request': request, 'output': output_name, 'operations': operations_record(ops, params)}
+    if masks:
+        info['masks'] = dict(masks)
     with open(os.path.join(out_dir, name + '.json'), 'w') as f:
         json.dump([info], f)
     return info
@@ -63,7 +109,13 @@ def main(argv=None):
     ap.add_argument('--multi_img', action='store_true', help='also write the picture after each operator')
     ap.add_argument('--proxy_short', type=int, default=600, help='short side of the picture the actor decides on')
     ap.add_argument('--save_dir', default='output/demo_output')
+    ap.add_argument('--mask', action='append', default=None, metavar='[NAME=]FILE',
+                    help='8-bit grey mask of the photo\'s size for a local edit (0 keeps, 255 edits); NAME = an operator name, '
+                         'without it the mask applies to every operator; repeatable, at most 4 files')
     args = ap.parse_args(argv)
+    named = parse_mask_args(args.mask)
+    img = decode_image(args.img)
+    masks = load_masks(named, img.shape[0], img.shape[1]) if named else None       # before the model: a wrong mask fails early
 
     from . import default_options
     from .actor import Actor
@@ -74,9 +126,9 @@ def main(argv=None):
     model = Actor(opt)
     model.load_state_dict(torch.load(args.checkpoint, map_location='cpu'), strict=False)      # as the demo (:129)
     model.to(device)
-    img = decode_image(args.img)
-    steps_u8, ops, params = edit_image(model, img, request_to_idx(args.request, vocab2id, opt), args.proxy_short)
-    info = write_outputs(args.save_dir, args.img, args.request, img, steps_u8.cpu().numpy(), ops, params.cpu(), args.multi_img)
+    steps_u8, ops, params = edit_image(model, img, request_to_idx(args.request, vocab2id, opt), args.proxy_short, masks=masks)
+    info = write_outputs(args.save_dir, args.img, args.request, img, steps_u8.cpu().numpy(), ops, params.cpu(), args.multi_img,
+                         masks=named or None)
     print('%s: %s -> %s' % (args.request, ', '.join(n for n, _ in info['operations']) or '(no operator)',
                             os.path.join(args.save_dir, os.path.splitext(os.path.basename(args.img))[0], info['output'])))
     return info

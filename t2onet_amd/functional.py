@@ -1992,3 +1992,63 @@ def replay_u8(src_u8, jobs, params, out=None):
     rc = _lib.load().t2o_replay_u8(_ptr(src_u8), _ptr(out), replay_jobs(jobs), len(jobs), _ptr(params), _stream(src_u8.device))
     replay_status(rc)
     return out
+
+
+REPLAY_MAX_MASKS = 4
+
+
+def replay_mask_table(jobs):
+    """The (J, 8) per-step mask indices of `jobs` (6-tuples, see replay_u8_masked) as the ctypes int array
+    t2o_replay_u8_masked takes: -1 where a job's mask_of is shorter than 8."""
+    arr = (ctypes.c_int * (REPLAY_MAX_STEPS * len(jobs)))(*([-1] * (REPLAY_MAX_STEPS * len(jobs))))
+    for j, job in enumerate(jobs):
+        for k, i in enumerate(list(job[5])[:REPLAY_MAX_STEPS]):
+            arr[REPLAY_MAX_STEPS * j + k] = int(i)
+    return arr
+
+
+def replay_u8_masked(src_u8, jobs, params, masks_u8, mask_offsets, out=None):
+    """replay_u8 with Operator.execute's mask operand -- a LOCAL edit at native size, ONE launch (t2o_replay_u8_masked):
+    job j = (src_offset, out_offset, h, w, ops, mask_of), mask_of[k] being an index into mask_offsets or -1; mask i is an
+    (h, w) uint8 plane of the job's own size at byte mask_offsets[i] of the 1-D uint8 GPU tensor masks_u8 (any alignment,
+    at most 4, shared by the jobs): 0 leaves a pixel, 255 applies the operator, values between feather the edge.  Step k
+    computes clamp(o * m + x * (1 - m), 0, 1) with m = byte / 255 where it names a mask, clamp(o, 0, 1) where it names
+    none.  The bytes equal resize_u8 at the picture's size -> operator_apply(op, x, param, mask (1,1,h,w) fp32) per step ->
+    to_u8_hwc.  Returns out (1-D uint8)."""
+    if not (torch.is_tensor(src_u8) and src_u8.is_cuda and src_u8.dtype == torch.uint8 and src_u8.is_contiguous()):
+        raise ValueError('replay_u8_masked: src must be a contiguous uint8 GPU tensor')
+    mask_offsets = [int(o) for o in mask_offsets]
+    if len(mask_offsets) > REPLAY_MAX_MASKS:
+        raise ValueError('replay_u8_masked: at most 4 masks per launch, got %d' % len(mask_offsets))
+    if mask_offsets and not (torch.is_tensor(masks_u8) and masks_u8.is_cuda and masks_u8.dtype == torch.uint8
+                             and masks_u8.is_contiguous() and masks_u8.device == src_u8.device):
+        raise ValueError('replay_u8_masked: masks must be a contiguous uint8 GPU tensor on the source\'s device')
+    jobs = [tuple(j) for j in jobs]
+    for j, (so, oo, h, w, ops, mask_of) in enumerate(jobs):
+        if len(mask_of) > len(ops):
+            raise ValueError('replay_u8_masked: job %d names %d masks for %d steps' % (j, len(mask_of), len(ops)))
+        if not (h > 0 and w > 0):
+            continue                                             # the library refuses it
+        if not (0 <= so and so + 3 * h * w <= src_u8.numel()):
+            raise ValueError('replay_u8_masked: job %d reads outside the %d-byte source' % (j, src_u8.numel()))
+        for i in mask_of:
+            if 0 <= i < len(mask_offsets) and not (0 <= mask_offsets[i] and mask_offsets[i] + h * w <= masks_u8.numel()):
+                raise ValueError('replay_u8_masked: job %d reads mask %d outside the %d-byte mask buffer' % (j, i, masks_u8.numel()))
+    need = max([oo + 3 * h * w for _, oo, h, w, _, _ in jobs if h > 0 and w > 0] or [1])
+    if out is None:
+        out = torch.empty(need, dtype=torch.uint8, device=src_u8.device)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == src_u8.device):
+        raise ValueError('replay_u8_masked: out must be a contiguous uint8 GPU tensor on the source\'s device')
+    elif out.numel() < need or any(j[1] < 0 for j in jobs):
+        raise ValueError('replay_u8_masked: a job writes outside the %d-byte output' % out.numel())
+    if params is not None:
+        _need_gpu(params)
+        params = params.contiguous()
+        if tuple(params.shape) != (len(jobs), REPLAY_MAX_STEPS, PARAM_PAD):
+            raise ValueError('replay_u8_masked: params must be (J, 8, 24), got %s' % (tuple(params.shape),))
+    offs = (ctypes.c_longlong * max(len(mask_offsets), 1))(*mask_offsets)
+    rc = _lib.load().t2o_replay_u8_masked(_ptr(src_u8), _ptr(out), replay_jobs([j[:5] for j in jobs]), replay_mask_table(jobs),
+                                          len(jobs), _ptr(params), _ptr(masks_u8) if mask_offsets else None, offs,
+                                          len(mask_offsets), _stream(src_u8.device))
+    replay_status(rc, 't2o_replay_u8_masked')
+    return out
