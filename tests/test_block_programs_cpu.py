@@ -71,6 +71,8 @@ def test_forward_backward_vs_oracle(op, shape):
 
 
 def test_identity_and_dynamic_batch():
+    """Per-sample operators (OP_DYNAMIC) in one batch, without a mask, with a soft 1-channel and with a hard 3-channel
+    mask: every sample against the fp64 oracle of its own operator; the identity sample ignores its mask."""
     B, H, W = 9, 24, 20
     img = synth.images(B, H, W, 71)
     gout = synth.uniform((B, 3, H, W), 72, -1.0, 1.0)
@@ -79,39 +81,47 @@ def test_identity_and_dynamic_batch():
     for b, op in enumerate(ops):
         if op >= 0:
             params[b, :cpu_ref.OP_NPARAM[op]] = synth.op_params(op, 1, 500 + b, 'mid')[0]
-    out, _ = emul.fwd(-2, img.numpy(), params.numpy(), op_id=ops)
-    gi, gp = emul.bwd(-2, img.numpy(), params.numpy(), gout.numpy(), op_id=ops)
-    for b, op in enumerate(ops):
-        if op < 0:
-            np.testing.assert_array_equal(out[b], img[b].numpy())
-            np.testing.assert_array_equal(gi[b], gout[b].numpy())
-            continue
-        n = cpu_ref.OP_NPARAM[op]
-        o_ref, gi_ref, gp_ref = oracle_fwd_bwd(op, img[b:b + 1], params[b:b + 1, :n], None, gout[b:b + 1], torch.float64)
-        np.testing.assert_allclose(out[b], o_ref[0].numpy(), rtol=0, atol=1e-6)
-        np.testing.assert_allclose(gi[b], gi_ref[0].numpy(), rtol=1e-5, atol=2e-6)
-        np.testing.assert_allclose(gp[b, :n], gp_ref[0].numpy(), rtol=1e-4, atol=2e-5 * max(1.0, float(gp_ref.abs().max())))
-        assert np.all(gp[b, n:] == 0)
+    for mask in (None, synth.masks(B, 1, H, W, 73), synth.masks(B, 3, H, W, 74, soft=False)):
+        mnp = None if mask is None else mask.numpy()
+        out, _ = emul.fwd(-2, img.numpy(), params.numpy(), mask=mnp, op_id=ops)
+        gi, gp = emul.bwd(-2, img.numpy(), params.numpy(), gout.numpy(), mask=mnp, op_id=ops)
+        for b, op in enumerate(ops):
+            if op < 0:
+                np.testing.assert_array_equal(out[b], img[b].numpy())
+                np.testing.assert_array_equal(gi[b], gout[b].numpy())
+                assert np.all(gp[b] == 0)
+                continue
+            n = cpu_ref.OP_NPARAM[op]
+            mb = None if mask is None else mask[b:b + 1]
+            o_ref, gi_ref, gp_ref = oracle_fwd_bwd(op, img[b:b + 1], params[b:b + 1, :n], mb, gout[b:b + 1], torch.float64)
+            np.testing.assert_allclose(out[b], o_ref[0].numpy(), rtol=0, atol=1e-6)
+            np.testing.assert_allclose(gi[b], gi_ref[0].numpy(), rtol=1e-5, atol=2e-6)
+            np.testing.assert_allclose(gp[b, :n], gp_ref[0].numpy(), rtol=1e-4, atol=2e-5 * max(1.0, float(gp_ref.abs().max())))
+            assert np.all(gp[b, n:] == 0)
 
 
 @pytest.mark.parametrize('op', [0, 1, 2, 3, 5, 6, -1])
 def test_fused_l1(op):
+    """Operator + L1 in one pass (target instead of gout), without a mask and with a soft 1-channel / hard 3-channel one."""
     B, H, W = 2, 20, 36
     img = synth.images(B, H, W, 81)
     tgt = synth.images(B, H, W, 82)
     n = cpu_ref.OP_NPARAM[op] if op >= 0 else 1
     p = synth.op_params(max(op, 0), B, 83, 'mid')
-    x = img.double().clone().requires_grad_(True)
-    pp = p.double().clone().requires_grad_(True)
-    out = x if op < 0 else operator_apply64(op, x, pp, None)
-    loss = (out - tgt.double()).abs().mean()
-    (loss * 3.0).backward()
-    o, l = emul.fwd(op, img.numpy(), p.numpy(), target=tgt.numpy())
-    assert abs(l - loss.item()) < 1e-6
-    gi, gp = emul.bwd(op, img.numpy(), p.numpy(), target=tgt.numpy(), gloss=3.0)
-    np.testing.assert_allclose(gi, x.grad.numpy(), rtol=1e-5, atol=1e-8)
-    if op >= 0:
-        np.testing.assert_allclose(gp, pp.grad.numpy(), rtol=1e-4, atol=1e-7)
+    for mask in (None, synth.masks(B, 1, H, W, 84), synth.masks(B, 3, H, W, 85, soft=False)):
+        mnp = None if mask is None else mask.numpy()
+        x = img.double().clone().requires_grad_(True)
+        pp = p.double().clone().requires_grad_(True)
+        out = x if op < 0 else operator_apply64(op, x, pp, None if mask is None else mask.double())
+        loss = (out - tgt.double()).abs().mean()
+        (loss * 3.0).backward()
+        o, l = emul.fwd(op, img.numpy(), p.numpy(), mask=mnp, target=tgt.numpy())
+        np.testing.assert_allclose(o, out.detach().numpy(), rtol=0, atol=1e-6)
+        assert abs(l - loss.item()) < 1e-6
+        gi, gp = emul.bwd(op, img.numpy(), p.numpy(), mask=mnp, target=tgt.numpy(), gloss=3.0)
+        np.testing.assert_allclose(gi, x.grad.numpy(), rtol=1e-5, atol=1e-8)
+        if op >= 0:
+            np.testing.assert_allclose(gp, pp.grad.numpy(), rtol=1e-4, atol=1e-7)
 
 
 @pytest.mark.parametrize('ops', [[0, 1, 2, 3, 5, 6], [5, 3, 5, 3, 0, 1, 2, 6], [6, 0, -1, 6, 3], [1], [6], [-1, -1],
