@@ -796,6 +796,40 @@ size_t t2o_end_select_var_mean_workspace_bytes(size_t row);
 int t2o_end_select_var_mean(const float* const* imgs, const long long* const* first, int R, int T, int B,
                             size_t row, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- local-edit masks on the device (t2o_mask.hip): GIER's COCO run-length masks, resized and unioned without a
+ * native-size plane, and the per-step mask of a masked episode chosen from the operator the decoder has just picked ----
+ * t2o_rle_union_u8: resize_and_union_mask of data/GIER/GIER.py:288-307 for n_jobs output planes in ONE launch.  A mask is
+ * COCO run lengths (column-major over [h, w], zeros first) given as CUMULATIVE run ends: mask m's are
+ * ends[first_end .. first_end + n_runs), the last one h * w.  Job j writes the (out_h, out_w) uint8 plane at byte
+ * out_offset of `out` (any alignment; planes may abut; no byte outside a plane is written): pixel (oy, ox) is the SUM, over
+ * the masks sel[first_sel .. first_sel + n_sel), of the mask's value at source pixel sy = min(floor(oy * (h / out_h)), h - 1),
+ * sx likewise (double; OpenCV's INTER_NEAREST rule) -- a count, as the reference's masks.sum(0): overlapping masks give 2, a
+ * repeated index counts twice, an empty selection gives 0; the sum saturates at 255.
+ * The four tables lie back to back in one buffer: n_jobs t2o_union_job_t, n_masks t2o_rle_mask_t, n_sel ints, n_ends
+ * unsigned ints.  host_tables: the buffer as the HOST holds it (read here, for the checks); dev_tables: the same bytes on the
+ * DEVICE (read by the kernel); both 8-byte aligned.  T2O_EINVAL, before any launch: null pointers, n_jobs outside 1..65535,
+ * sizes that are not positive, h * w >= 2^31, run ends that decrease or do not end at h * w, runs outside the run array, a
+ * selection index outside the mask table, a selection outside the list, a plane outside [0, out_bytes).
+ * No allocation, no host synchronisation, capturable, deterministic. */
+typedef struct {
+  unsigned int first_end;             /* index of the mask's first cumulative run end */
+  int n_runs, h, w;
+} t2o_rle_mask_t;
+typedef struct {
+  int first_sel, n_sel;
+  int out_h, out_w;
+  long long out_offset;
+} t2o_union_job_t;
+int t2o_rle_union_u8(const void* host_tables, const void* dev_tables, int n_jobs, int n_masks, int n_sel, long long n_ends,
+                     unsigned char* out, long long out_bytes, void* stream);
+
+/* get_gt_mask of models/actor.py:78-98 from device values.  planes: (N,H,W) uint8; slot: (B,V) int32, a plane number or -1;
+ * pred_op: (B) int64; out: (B,1,H,W) fp32 = float(planes[slot[b][pred_op[b]]]), all ones where the slot is -1 (or not a
+ * plane number) or pred_op[b] lies outside [0, V): no entry means a global edit.  One launch, any H, W >= 1, B <= 65535;
+ * planes may be NULL when N = 0. */
+int t2o_mask_select(const unsigned char* planes, const int* slot, const long long* pred_op, float* out, int N, int B, int V,
+                    int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,15 @@ class Actor(nn.Module):
             masks.append(torch.ones_like(img[i]) if mask is None else mask)
         return torch.stack(masks, dim=0)
 
+    def step_mask(self, img, mask_dict, pred_op):
+        """The mask of one decoding step.  A gier.MaskTable: ONE functional.mask_select on the device-resident pred_op ->
+        (B,1,H,W), no host read and no loop over samples.  A list of dicts: get_gt_mask -> (B,3,H,W), one host read."""
+        if hasattr(mask_dict, 'planes') and hasattr(mask_dict, 'slot'):
+            if tuple(mask_dict.size) != tuple(img.shape[-2:]) or mask_dict.slot.shape[0] != img.shape[0]:
+                raise ValueError('MaskTable of %d samples at %s for images %s' % (mask_dict.slot.shape[0], mask_dict.size, tuple(img.shape)))
+            return T.mask_select(mask_dict.planes, mask_dict.slot, pred_op.detach())
+        return self.get_gt_mask(img, mask_dict, pred_op.detach().cpu().numpy())
+
     def divide_op_group(self, ops):
         """Kept for API compatibility (actor.py:100-114); the forward passes do not use it."""
         unqs = torch.unique(ops)
@@ -252,8 +261,8 @@ class Actor(nn.Module):
                     pred_op = probs.topk(1)[1].view(B, -1)
                 op_mask.scatter_(1, pred_op, 0.0)          # an operator is used at most once
             pred_mask = None
-            if mask_dict is not None:                      # local edits (GIER): one host sync per step, as the reference
-                pred_mask = self.get_gt_mask(img_x, mask_dict, pred_op.detach().cpu().numpy())
+            if mask_dict is not None:                      # local edits (GIER): a MaskTable stays on the device; a list of
+                pred_mask = self.step_mask(img_x, mask_dict, pred_op)      # dicts costs one host sync per step, as the reference
                 pred_masks.append(pred_mask)
             img_x, par = self._execute(img_x, pred_op, context, pred_mask, exec_op)
             pred_imgs.append(img_x)
@@ -283,7 +292,7 @@ class Actor(nn.Module):
         probs = probs * op_mask
         probs = probs / (probs.sum(1, keepdim=True) + 1e-30)
         pred_op = sample_categorical(probs)
-        pred_mask = self.get_gt_mask(img_x, mask_dict, pred_op.detach().cpu().numpy()) if mask_dict is not None else None
+        pred_mask = self.step_mask(img_x, mask_dict, pred_op) if mask_dict is not None else None
         pred_img, _ = self._execute(img_x, pred_op, context, pred_mask)
         _, _, _, next_context = self.decoder.forward_step(pred_op, dec_hidden, enc_out, self.image_features(pred_img))
         return pred_img, logp, entropy_penalty, context, next_context

@@ -184,13 +184,14 @@ class DeviceEvaluator(object):
         return dict(in_L1=avg[0], out_L1=avg[1], in_SSIM=avg[2], out_SSIM=avg[3])
 
 
-def test_on_device(model, loader, opt, is_test=False, device=None, verbose=True, on_batch=None):
+def test_on_device(model, loader, opt, is_test=False, device=None, verbose=True, on_batch=None, mask_fn=None):
     """The loop of test() with nothing between two images that depends on a device value: the arg-max episode returns its
     step images as a list (stack=False), the END step is an index tensor (train.first_end_step) and ONE eval_metrics call per
     batch writes the two L1 distances -- and with is_test the two SSIM values -- into a DeviceEvaluator's table, read once
     after the loop (the progress line every opt.print_every batches reads the rows written so far).
     on_batch(itr, data, pred_imgs, first, pred_ops, pred_params): called after each batch's launches (test_cli saves pictures
-    there).  Returns (avg_init_dist, avg_dist, metrics) with metrics = the dict of ImageEvaluator.eval() (None unless
+    there).  mask_fn(data, img_x): the batch's `mask_dict` for the episode -- a gier.MaskTable keeps the loop free of host
+    reads, a list of dicts costs one per step; None (the default): global edits.  Returns (avg_init_dist, avg_dist, metrics) with metrics = the dict of ImageEvaluator.eval() (None unless
     is_test)."""
     model.eval()
     device = device or next(model.parameters()).device
@@ -202,7 +203,8 @@ def test_on_device(model, loader, opt, is_test=False, device=None, verbose=True,
         lengths = (x != opt.null_id).sum(1)                      # on the host, before the copy
         x, img_x, img_y = (t.to(device, non_blocking=True) for t in (x, img_x, img_y))
         with torch.no_grad():
-            _, pred_imgs, pred_ops, pred_params = single.episode_forward(x, img_x, None, reinforce_sample=False, lengths=lengths,
+            mask_dict = None if mask_fn is None else mask_fn(data, img_x)
+            _, pred_imgs, pred_ops, pred_params = single.episode_forward(x, img_x, mask_dict, reinforce_sample=False, lengths=lengths,
                                                                          stack=False)
             first = first_end_step(pred_ops, opt.end_id)
             evaluator.update(img_x, pred_imgs, first, img_y)

@@ -2052,3 +2052,104 @@ def replay_u8_masked(src_u8, jobs, params, masks_u8, mask_offsets, out=None):
                                           len(mask_offsets), _stream(src_u8.device))
     replay_status(rc, 't2o_replay_u8_masked')
     return out
+
+
+# ---- local-edit masks (t2o_mask.hip): run-length masks resized and unioned on the device; the per-step mask select ----
+
+RLE_MASK = np.dtype([('first_end', '<u4'), ('n_runs', '<i4'), ('h', '<i4'), ('w', '<i4')])                    # t2o_rle_mask_t
+UNION_JOB = np.dtype([('first_sel', '<i4'), ('n_sel', '<i4'), ('out_h', '<i4'), ('out_w', '<i4'), ('out_offset', '<i8')])   # t2o_union_job_t
+
+
+class RleTables(object):
+    """The packed tables of a t2o_rle_union_u8 launch: .host (1-D uint8 CPU tensor, pinned when a GPU is there) = jobs, masks,
+    selection, cumulative run ends back to back, then `extra` (int32 values that travel in the same upload), .counts =
+    (n_jobs, n_masks, n_sel, n_ends), .need = bytes of output the jobs cover, .dev = the device copy once uploaded."""
+
+    def __init__(self, host, counts, need, extra_at, extra_n):
+        self.host, self.counts, self.need, self.extra_at, self.extra_n, self.dev = host, counts, need, extra_at, extra_n, None
+
+    def upload(self, device=None):
+        if self.dev is None:
+            if device is None:
+                device = torch.device('cuda', torch.cuda.current_device())
+            self.dev = self.host.to(device, non_blocking=True)
+        return self.dev
+
+    def extra(self):
+        return self.dev[self.extra_at:self.extra_at + 4 * self.extra_n].view(torch.int32)
+
+
+def pack_rle_union(masks, jobs, extra=None, pin=None):
+    """masks: COCO RLE dicts {'size': [h, w], 'counts': string or list} or (counts, h, w) tuples; jobs: (mask indices,
+    out_offset, out_h, out_w) per output plane -> RleTables.  Parsing (gier.rle_counts) and the running sums happen here."""
+    from .gier import rle_counts
+    ends, mrec, first = [], np.zeros(len(masks), RLE_MASK), 0
+    for i, m in enumerate(masks):
+        if isinstance(m, dict):
+            counts, h, w = rle_counts(m), int(m['size'][0]), int(m['size'][1])
+        else:
+            counts, h, w = np.asarray(m[0], dtype=np.int64).astype(np.uint32), int(m[1]), int(m[2])
+        ends.append(np.cumsum(counts, dtype=np.uint64).astype(np.uint32))
+        mrec[i] = (first, len(counts), h, w)
+        first += len(counts)
+    jrec, sel = np.zeros(len(jobs), UNION_JOB), []
+    need = 1
+    for i, (ids, off, oh, ow) in enumerate(jobs):
+        jrec[i] = (len(sel), len(ids), int(oh), int(ow), int(off))
+        sel.extend(int(k) for k in ids)
+        need = max(need, int(off) + max(int(oh), 0) * max(int(ow), 0))
+    sel = np.asarray(sel, dtype=np.int32)
+    ends = np.concatenate(ends) if ends else np.zeros(0, np.uint32)
+    extra = np.zeros(0, np.int32) if extra is None else np.ascontiguousarray(extra, dtype=np.int32).reshape(-1)
+    parts = [jrec.view(np.uint8), mrec.view(np.uint8), sel.view(np.uint8), ends.view(np.uint8), extra.view(np.uint8)]
+    total = sum(p.size for p in parts)
+    host = torch.empty(max(total, 8), dtype=torch.uint8, pin_memory=torch.cuda.is_available() if pin is None else bool(pin))
+    flat, pos = host.numpy(), 0
+    for p in parts:
+        flat[pos:pos + p.size] = p.reshape(-1)
+        pos += p.size
+    return RleTables(host, (len(jobs), len(masks), int(sel.size), int(ends.size)), need, total - 4 * extra.size, int(extra.size))
+
+
+def rle_union_u8(masks, jobs=None, device=None, out=None, extra=None):
+    """resize_and_union_mask (data/GIER/GIER.py:288-307) for every plane of a batch in ONE launch, from run lengths
+    (t2o_rle_union_u8): job j = (mask indices, out_offset, out_h, out_w) writes, at byte out_offset of the 1-D uint8 GPU
+    tensor `out` (allocated to fit when None; any alignment, planes may abut), the uint8 plane whose pixel (oy, ox) is the
+    SUM over the job's masks of the mask's value at the source pixel edit.nearest_index names -- a count: overlapping masks
+    give 2, a repeated index counts twice, an empty list gives zeros; saturating at 255.  masks: RLE dicts / (counts, h, w)
+    tuples, or an RleTables from pack_rle_union (jobs is then None; already uploaded tables are launched as they are, e.g.
+    inside a graph capture).  One pinned buffer, one upload, one launch on the current stream; nothing waits on the host.
+    extra: int32 values to ride in the same upload; returns (out, their device copy) then, else out."""
+    tables = masks if isinstance(masks, RleTables) else pack_rle_union(masks, jobs, extra)
+    if tables.dev is None:
+        tables.upload(device if device is not None else (out.device if out is not None else None))
+    dev = tables.dev.device
+    if out is None:
+        out = torch.empty(tables.need, dtype=torch.uint8, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == dev):
+        raise ValueError('rle_union_u8: out must be a contiguous uint8 GPU tensor on the tables\' device')
+    n_jobs, n_masks, n_sel, n_ends = tables.counts
+    rc = _lib.load().t2o_rle_union_u8(tables.host.data_ptr(), tables.dev.data_ptr(), n_jobs, n_masks, n_sel, n_ends, _ptr(out),
+                                      out.numel(), _stream(dev))
+    replay_status(rc, 't2o_rle_union_u8')
+    return (out, tables.extra()) if extra is not None else out
+
+
+def mask_select(planes, slot, pred_op):
+    """Actor.get_gt_mask from device values (t2o_mask_select): planes (N,H,W) uint8, slot (B,V) int32 -- a plane number or
+    -1 --, pred_op (B,) or (B,1) int64, all on the GPU -> (B,1,H,W) fp32 = float(planes[slot[b][pred_op[b]]]), all ones where
+    the slot is -1 or the operator lies outside [0, V): no entry means a global edit.  One launch, no host read."""
+    if not (planes.is_cuda and planes.dtype == torch.uint8 and planes.dim() == 3 and planes.is_contiguous()):
+        raise RuntimeError('mask_select: planes must be a contiguous (N,H,W) uint8 GPU tensor; there is no CPU implementation')
+    if not (slot.is_cuda and slot.dtype == torch.int32 and slot.dim() == 2 and slot.is_contiguous()):
+        raise RuntimeError('mask_select: slot must be a contiguous (B,V) int32 GPU tensor')
+    pred_op = pred_op.reshape(-1)
+    if not (pred_op.is_cuda and pred_op.dtype == torch.int64 and pred_op.is_contiguous() and pred_op.numel() == slot.shape[0]):
+        raise RuntimeError('mask_select: pred_op must be a contiguous int64 GPU tensor of B elements')
+    N, H, W = planes.shape
+    B, V = slot.shape
+    out = torch.empty(B, 1, H, W, dtype=torch.float32, device=planes.device)
+    rc = _lib.load().t2o_mask_select(_ptr(planes) if N else None, _ptr(slot), _ptr(pred_op), _ptr(out), N, B, V, H, W,
+                                     _stream(planes.device))
+    replay_status(rc, 't2o_mask_select')
+    return out

@@ -9,7 +9,10 @@ word vectors (fix_input_embedding) -- synthetic runs train the whole table inste
     python -m t2onet_amd.train_cli --synthetic --batch_size 64 --num_iters 100
     python -m torch.distributed.run --nproc-per-node 8 -m t2onet_amd.train_cli --synthetic ...   # data parallel
 
-Real data: --img_dir/--anno_dir/--act_dir with the reference's FiveK layout (datasets/FiveKdataset.py).
+Real data: --img_dir/--anno_dir/--act_dir with the reference's FiveK layout (datasets/FiveKdataset.py), or
+--dataset GIER --data_dir data/GIER --act_dir output/GIER_actions_set_1 --data_mode valid [--session 3] with the reference's
+GIER layout (train_GIER_seq2seqL1.py: gier.GIERDatasetAct for training, gier.GIERDataset('val') for validation, GIER's
+vocabularies, global edits only).
 """
 import argparse
 import json
@@ -62,9 +65,14 @@ def sync_batchnorm_buffers(model, world):
             buf.div_(world)
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--synthetic', action='store_true')
+    ap.add_argument('--dataset', default='FiveK', choices=['FiveK', 'GIER'])
+    ap.add_argument('--data_dir', default='data/GIER', help='GIER: the directory holding images/, masks/ and splits/')
+    ap.add_argument('--data_mode', default='valid', help='GIER: split families joined with +')
+    ap.add_argument('--vocab_dir', default='data/language')
+    ap.add_argument('--session', type=int, default=None, help='default: 1 (FiveK), 3 (GIER)')
     ap.add_argument('--img_dir', default='data/FiveK/images')
     ap.add_argument('--anno_dir', default='data/FiveK/annotations')
     ap.add_argument('--act_dir', default='output/actions_set_1')
@@ -85,6 +93,16 @@ def main(argv=None):
     ap.add_argument('--device_eval', action='store_true',
                     help='validation through evaluate.test_on_device: one fused metrics launch per image, one host read per pass')
     args = ap.parse_args(argv)
+    if args.session is None:
+        args.session = 3 if args.dataset == 'GIER' else 1
+    if args.dataset == 'GIER' and (args.synthetic or args.device_resize):
+        ap.error('--dataset GIER reads a GIER tree on the host: neither --synthetic nor --device_resize')
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    gier_run = args.dataset == 'GIER'
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -101,7 +119,8 @@ def main(argv=None):
         raise SystemExit('train_cli: --word2vec is required with real data: the reference freezes the GloVe word rows '
                          '(fix_input_embedding=1, lang_encoder.py:22-31); freezing random rows would train nothing there')
     opt = default_options(batch_size=args.batch_size, learning_rate=args.learning_rate, print_every=args.print_every,
-                          fix_input_embedding=1 if word2vec is not None else 0)
+                          fix_input_embedding=1 if word2vec is not None else 0,
+                          **(dict(dataset='GIER', session=args.session, vocab_dir=args.vocab_dir) if gier_run else {}))
     model = Actor(opt, word2vec=word2vec).to(device).train()
     if not args.eager:
         model.use_channels_last()
@@ -109,13 +128,23 @@ def main(argv=None):
     torch.manual_seed(args.manual_seed + 1000 * rank)        # independent sampling / dropout streams per rank
 
     raw = args.device_resize and not args.synthetic
-    dataset = SyntheticFiveK(n=args.batch_size * 64, size=args.img_size) if args.synthetic else \
-        FiveKAct(args.img_dir, args.anno_dir, args.act_dir, 'train', 1, args.img_size, raw=raw)
+    if gier_run:
+        # train_GIER_seq2seqL1.py:157-164: GIERDatasetAct for training, GIERDataset('val') for validation, is_load_mask = False
+        # (global edits only); the vocabularies are GIER's (options.dataset -> actor._vocab_sizes)
+        from .gier import GIERDataset, GIERDatasetAct, _Tuples
+        dataset = _Tuples(GIERDatasetAct(args.data_dir, args.vocab_dir, args.act_dir, 'train', args.data_mode, False, args.session,
+                                         args.img_size))
+    else:
+        dataset = SyntheticFiveK(n=args.batch_size * 64, size=args.img_size) if args.synthetic else \
+            FiveKAct(args.img_dir, args.anno_dir, args.act_dir, 'train', 1, args.img_size, raw=raw)
     sampler = DistributedSampler(dataset, world, rank, shuffle=True) if world > 1 else None
     raw_kw = dict(collate_fn=collate_raw, pin_memory=True) if raw else {}
     loader = DataLoader(dataset, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler,
                         num_workers=args.num_workers, drop_last=True, **raw_kw)
-    if args.synthetic:
+    if gier_run:
+        val_loader = DataLoader(_Tuples(GIERDataset(args.data_dir, args.vocab_dir, 'val', args.data_mode, False, args.session)),
+                                batch_size=1, shuffle=False, num_workers=1)
+    elif args.synthetic:
         val_loader = DataLoader(_EvalView(SyntheticFiveK(n=args.val_items, size=args.img_size, seed=args.manual_seed + 1)),
                                 batch_size=args.batch_size, shuffle=False, num_workers=args.num_workers)
     else:
