@@ -770,6 +770,42 @@ int t2o_replay_u8_masked(const unsigned char* src, unsigned char* out, const t2o
                          const float* params, const unsigned char* masks, const long long* mask_offsets, int n_masks,
                          void* stream);
 
+/* ---- feathering the mask planes of a local edit on the device (t2o_feather.hip): a hard 0/255 selection gets the soft
+ * edge a photo wants.  Job j blurs the (h,w) uint8 plane at src + src_offset (any byte alignment) with a separable
+ * Gaussian of standard deviation sigma (pixels of the plane, 0 <= sigma <= 64) in INTEGER arithmetic with replicated
+ * borders and writes (h,w) uint8 at out + out_offset (any byte alignment; no byte outside the plane is written).
+ * Weights (t2o_feather_weights, host only, fp64): R0 = min(ceil(3 sigma), 192); g_i = exp(-i^2 / (2 sigma^2)) for
+ * i = 0..R0; G = g_0 + 2 sum_{i>=1} g_i; e_i = 65536 g_i / G; tail sums T_i = sum_{k=i..R0} e_k, T_{R0+1} = 0;
+ *   w_i = rint(T_i) - rint(T_{i+1}) for i >= 1,   w_0 = 65536 - 2 rint(T_1);
+ * trailing zero weights are trimmed, which gives the radius R.  So w_0 + 2 sum_{i>=1} w_i = 65536 exactly, every
+ * w_i >= 0 and |w_i - e_i| <= 1.  R = 0 (sigma = 0, or at or below about 0.2) is w_0 = 65536, a plain copy; otherwise
+ * w_0 <= 65534 and the weights are uint16 (w[0] holds 0, 65536 modulo 2^16, when R = 0).
+ *   row pass     a = sum_{i=-R..R} w_|i| m[y, clamp(x+i, 0, w-1)] <= 255 * 65536;     t = (a + 128) >> 8 <= 65280, uint16
+ *   column pass  b = sum_{i=-R..R} w_|i| t[clamp(y+i, 0, h-1), x] <= 65280 * 65536;   out = (b + 2^23) >> 24
+ * in unsigned 32-bit arithmetic, exact.  A constant plane comes out unchanged, the output lies within [min m, max m],
+ * and flipping the input in both axes flips the output; the intermediate is rounded after the row pass, so the
+ * transposed input does not give the transposed output in general.
+ * Two launches cover all jobs; every source byte is read by the first before the second writes any destination byte, so
+ * a job may run in place (out + out_offset == src + src_offset) and a source may overlap any destination; the
+ * destinations of different jobs may not overlap each other.  jobs: HOST array of 1 <= J <= 4, copied with the weights
+ * into the kernel arguments.  workspace: DEVICE, 8-byte aligned, t2o_feather_workspace_bytes (2 bytes per pixel, rows
+ * padded to 4 pixels; 0 for a job table that t2o_feather_u8 would refuse).  No allocation, no host synchronisation, no
+ * float, no atomics; deterministic, capturable.  The caller guarantees that offsets and sizes lie inside src / out.
+ * T2O_EINVAL, before any launch: null pointers, J outside 1..4, sigma negative, NaN or above 64, non-positive sizes,
+ * h * w >= 2^31, negative offsets, overlapping destinations.  T2O_EWORKSPACE: workspace null or too small. */
+#define T2O_FEATHER_MAX_SIGMA 64.0
+#define T2O_FEATHER_MAX_RADIUS 192
+#define T2O_FEATHER_MAX_JOBS 4
+typedef struct {
+  long long src_offset, out_offset;   /* first byte of the source / destination plane, counted from src / out */
+  int h, w;
+  double sigma;
+} t2o_feather_job_t;
+int t2o_feather_weights(double sigma, unsigned short* w /* 193 */, int* radius);
+size_t t2o_feather_workspace_bytes(const t2o_feather_job_t* jobs, int J);
+int t2o_feather_u8(const unsigned char* src, unsigned char* out, const t2o_feather_job_t* jobs, int J, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
 /* ---- the metrics of the test loop in one call: utils/eval.py:50-60 (ImageEvaluator.update: input / output L1 and SSIM),
  * utils/ssim/__init__.py:20-40 (the SSIM itself) and test_seq2seqL1.py:60-74 (the END-image select and the two L1
  * distances the loop averages).  imgs: HOST array of 1 <= T <= 8 device pointers to (B,C,H,W) step images, first: device

@@ -156,6 +156,9 @@ SIGNATURES = {
     't2o_f32_to_u8_hwc': (_I, [_P, _I, _I, _I, _P, _P]),
     't2o_replay_u8': (_I, [_P, _P, _P, _I, _P, _P]),
     't2o_replay_u8_masked': (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
+    't2o_feather_weights': (_I, [_D, _P, _P]),
+    't2o_feather_workspace_bytes': (_Z, [_P, _I]),
+    't2o_feather_u8': (_I, [_P, _P, _P, _I, _P, _Z, _P]),
     't2o_eval_metrics_workspace_bytes': (_Z, [_I, _I, _I, _I]),
     't2o_eval_metrics': (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _Z, _I, _I, _I, _I, _P]),
     't2o_end_select_var_mean_workspace_bytes': (_Z, [_Z]),

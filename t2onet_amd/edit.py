@@ -31,10 +31,10 @@ def nearest_index(src, dst):
     return np.minimum(np.floor(np.arange(dst, dtype=np.float64) * scale).astype(np.int64), src - 1)
 
 
-def _checked_masks(masks, h, w):
+def _checked_masks(masks, h, w, slots=None):
     """masks {executor operator index or 'all': uint8 (h, w)} -> ([distinct planes], {operator index: plane number}).
     'all' stands for every operator the actor can choose (actor.OP_MASK); an entry for one operator wins over it; planes
-    that are the same object are uploaded once."""
+    that are the same object are uploaded once.  slots: a dict that receives {id of the mask object: plane number}."""
     planes, slot_of, by_op = [], {}, {}
     for key in sorted(masks, key=lambda k: (k != 'all', str(k))):              # 'all' first, so that named entries overwrite it
         a = masks[key].numpy() if torch.is_tensor(masks[key]) else np.asarray(masks[key])
@@ -53,7 +53,31 @@ def _checked_masks(masks, h, w):
             by_op[op] = slot_of[id(masks[key])]
     if len(planes) > T.REPLAY_MAX_MASKS:
         raise ValueError('edit_image: %d distinct masks, the replay takes %d' % (len(planes), T.REPLAY_MAX_MASKS))
+    if slots is not None:
+        slots.update(slot_of)
     return planes, by_op
+
+
+def checked_feather(feather, masks):
+    """feather (None, a number, or {key of masks: number}) -> {id of the mask object: sigma > 0}.  Two keys that name one
+    plane must agree; a sigma of 0 leaves its plane as it is."""
+    if feather is None:
+        return {}
+    if masks is None:
+        raise ValueError('edit_image: feather without masks -- there is no plane to feather')
+    if not isinstance(feather, dict):
+        feather = {key: feather for key in masks}
+    by_plane = {}
+    for key, sigma in feather.items():
+        if key not in masks:
+            raise ValueError('edit_image: feather key %r names no mask (masks: %s)' % (key, ', '.join(repr(k) for k in masks)))
+        sigma = float(sigma)
+        if not 0.0 <= sigma <= T.FEATHER_MAX_SIGMA:
+            raise ValueError('edit_image: feather %r = %r, a sigma must lie in [0, %g]' % (key, sigma, T.FEATHER_MAX_SIGMA))
+        if by_plane.setdefault(id(masks[key]), sigma) != sigma:
+            raise ValueError('edit_image: feather %r = %g, but another key feathers the same plane by %g'
+                             % (key, sigma, by_plane[id(masks[key])]))
+    return {plane: sigma for plane, sigma in by_plane.items() if sigma > 0.0}
 
 
 def _append_planes(buffer, planes):
@@ -79,7 +103,7 @@ def _proxy_mask_dict(dev_buffer, mask_offsets, by_op, size, proxy_size):
     return [{str(op + 3): [proxies[slot]] for op, slot in by_op.items()}]
 
 
-def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None):
+def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None):
     """img_u8_hwc: the decoded photo, uint8 (h,w,3) RGB (array or CPU tensor); x: (1, L) request token ids.
     Returns (steps_u8, ops, params):
       steps_u8  (max(n,1), h, w, 3) uint8 GPU tensor: picture k is the photo after the first k+1 of the n chosen operators,
@@ -94,17 +118,25 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None):
     operator the actor can choose, an entry for one operator wins over it.  The planes travel behind the photo in the same
     upload; the proxy sees each one through nearest_index (indexed on the device, / 255) as the mask_dict of
     Actor.get_gt_mask (one host read of the chosen operator per step, as the reference); ONE replay_u8_masked launch then
-    writes every prefix at native size under the native planes."""
+    writes every prefix at native size under the native planes.
+    feather: None, a standard deviation in pixels of the photo (every plane), or {key of masks: sigma} -- the planes are
+    blurred by functional.feather_u8's exact integer Gaussian IN PLACE on the device right after the upload (two launches,
+    whatever the number of planes), so that a hard 0/255 selection leaves no seam; the proxy's decision and the native
+    replay see the same soft mask.  Keys that share one plane must agree; feather without masks is an error."""
     img = T._u8_hwc(img_u8_hwc)
     h, w = img.shape[:2]
+    sigma_of = checked_feather(feather, masks)                  # before any device use
     dev = next(model.parameters()).device
     opt = model.opt
-    planes, by_op = _checked_masks(masks, h, w) if masks is not None else ([], {})
+    slot_of = {}
+    planes, by_op = _checked_masks(masks, h, w, slot_of) if masks is not None else ([], {})
     buffer, descs = T.pack_u8([img])
     mask_offsets = []
     if masks is not None:
         buffer, mask_offsets = _append_planes(buffer, planes)
     dev_buffer, table_ptr, descs, _keep = T.upload_packed(buffer, descs, dev)
+    if sigma_of:
+        T.feather_u8(dev_buffer, [(mask_offsets[slot_of[p]],) * 2 + (h, w, sigma) for p, sigma in sigma_of.items()])
     ph, pw = short_side_size(h, w, proxy_short) if min(h, w) > proxy_short else (h, w)
     proxy = T._resize_launch(dev_buffer, table_ptr, 1, ph, pw)
     mask_dict = None if masks is None else _proxy_mask_dict(dev_buffer, mask_offsets, by_op, (h, w), (ph, pw))

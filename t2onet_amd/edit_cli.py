@@ -12,6 +12,10 @@ leaves a pixel as it is, 255 applies the operator, values between feather the ed
 above and binds the mask to that operator; without a name the mask applies to every operator (a named mask wins).  At
 most 4 distinct files.  The record then also holds 'masks': {name or 'all': file}.
 
+--feather [NAME=]SIGMA (repeatable) blurs a mask on the device before it is used, by an exact 8-bit Gaussian of standard
+deviation SIGMA pixels of the photo (at most 64): the soft edge a hard 0/255 selection lacks.  NAME is a name a --mask was
+given under; without a name every mask is feathered.  The record then also holds 'feather': {name or 'all': sigma}.
+
 The actor decides on a proxy of the photo (short side --proxy_short, the test loader's 600; a smaller photo is its own
 proxy) and the decision is applied to the photo at its native size by the fused 8-bit replay kernel (edit.edit_image).
 
@@ -61,6 +65,41 @@ def parse_mask_args(specs):
     return named
 
 
+def parse_feather_args(specs, named):
+    """--feather values ([NAME=]SIGMA) -> {name or 'all': sigma}; named: what parse_mask_args returned.  NAME must be a
+    name a --mask was given under, SIGMA a number in [0, 64]; no NAME means every mask.  Raises ValueError."""
+    import math
+    sigmas = {}
+    for spec in specs or []:
+        head, sep, tail = spec.partition('=')
+        name, text = (head, tail) if sep else ('all', spec)
+        if not named:
+            raise ValueError('--feather %s: there is no --mask to feather' % spec)
+        if sep and name not in named:
+            raise ValueError('--feather %s: no --mask was given under %r (given: %s)' % (spec, name, ', '.join(sorted(named))))
+        try:
+            sigma = float(text)
+        except ValueError:
+            raise ValueError('--feather %s: %r is not a number' % (spec, text))
+        if math.isnan(sigma) or not 0.0 <= sigma <= 64.0:
+            raise ValueError('--feather %s: SIGMA must lie in [0, 64]' % spec)
+        sigmas[name] = sigma
+    return sigmas
+
+
+def feather_argument(sigmas, named):
+    """{name or 'all': sigma} of parse_feather_args -> the `feather` argument of edit.edit_image, keyed like the masks
+    load_masks returns for `named`.  An unnamed sigma stands for every mask; a named one wins over it.  Two names that
+    share one file must end up with one sigma (edit.checked_feather)."""
+    if not sigmas:
+        return None
+    feather = {}
+    for name in named:
+        if name in sigmas or 'all' in sigmas:
+            feather['all' if name == 'all' else ACTIONS.index(name)] = sigmas.get(name, sigmas.get('all'))
+    return feather
+
+
 def load_masks(named, h, w):
     """{name: file} -> the `masks` argument of edit.edit_image: every file decoded with PIL as 8-bit grey, one array per
     distinct file; a size other than the photo's (h, w) is an error naming both."""
@@ -78,9 +117,9 @@ def load_masks(named, h, w):
     return masks
 
 
-def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, multi_img=False, masks=None):
+def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, multi_img=False, masks=None, feather=None):
     """The files of one edit (see the module docstring); steps_u8: (max(n,1), h, w, 3) uint8 array; masks: {name: file}
-    of a local edit, recorded when given.  Returns the record."""
+    of a local edit and feather: {name: sigma}, each recorded when given.  Returns the record."""
     from PIL import Image
     name, ext = os.path.splitext(os.path.basename(img_path))
     out_dir = os.path.join(save_dir, name)
@@ -94,6 +133,8 @@ def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, mu
     info = {'input': input_name, 'request': request, 'output': output_name, 'operations': operations_record(ops, params)}
     if masks:
         info['masks'] = dict(masks)
+    if feather:
+        info['feather'] = dict(feather)
     with open(os.path.join(out_dir, name + '.json'), 'w') as f:
         json.dump([info], f)
     return info
@@ -112,10 +153,18 @@ def main(argv=None):
     ap.add_argument('--mask', action='append', default=None, metavar='[NAME=]FILE',
                     help='8-bit grey mask of the photo\'s size for a local edit (0 keeps, 255 edits); NAME = an operator name, '
                          'without it the mask applies to every operator; repeatable, at most 4 files')
+    ap.add_argument('--feather', action='append', default=None, metavar='[NAME=]SIGMA',
+                    help='blur a mask on the device by a Gaussian of SIGMA pixels (at most 64) before it is used; NAME = a name '
+                         'a --mask was given under, without it every mask; repeatable')
     args = ap.parse_args(argv)
     named = parse_mask_args(args.mask)
+    sigmas = parse_feather_args(args.feather, named)                               # before the model: a wrong value fails early
     img = decode_image(args.img)
     masks = load_masks(named, img.shape[0], img.shape[1]) if named else None       # before the model: a wrong mask fails early
+    feather = feather_argument(sigmas, named)
+    if feather:
+        from .edit import checked_feather
+        checked_feather(feather, masks)                                            # two names, one file, two sigmas
 
     from . import default_options
     from .actor import Actor
@@ -126,9 +175,10 @@ def main(argv=None):
     model = Actor(opt)
     model.load_state_dict(torch.load(args.checkpoint, map_location='cpu'), strict=False)      # as the demo (:129)
     model.to(device)
-    steps_u8, ops, params = edit_image(model, img, request_to_idx(args.request, vocab2id, opt), args.proxy_short, masks=masks)
+    steps_u8, ops, params = edit_image(model, img, request_to_idx(args.request, vocab2id, opt), args.proxy_short, masks=masks,
+                                      feather=feather)
     info = write_outputs(args.save_dir, args.img, args.request, img, steps_u8.cpu().numpy(), ops, params.cpu(), args.multi_img,
-                         masks=named or None)
+                         masks=named or None, feather=sigmas or None)
     print('%s: %s -> %s' % (args.request, ', '.join(n for n, _ in info['operations']) or '(no operator)',
                             os.path.join(args.save_dir, os.path.splitext(os.path.basename(args.img))[0], info['output'])))
     return info

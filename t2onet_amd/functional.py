@@ -2153,3 +2153,80 @@ def mask_select(planes, slot, pred_op):
                                      _stream(planes.device))
     replay_status(rc, 't2o_mask_select')
     return out
+
+
+# ---- mask feathering (t2o_feather.hip): the soft edge of a local edit, an exact integer Gaussian on uint8 planes ----
+
+FEATHER_MAX_JOBS, FEATHER_MAX_SIGMA, FEATHER_MAX_RADIUS = 4, 64.0, 192
+
+
+class FeatherJob(ctypes.Structure):
+    """t2o_feather_job_t of include/t2onet_hip.h (field for field)."""
+    _fields_ = [('src_offset', ctypes.c_longlong), ('out_offset', ctypes.c_longlong), ('h', ctypes.c_int), ('w', ctypes.c_int),
+                ('sigma', ctypes.c_double)]
+
+
+def feather_jobs(jobs):
+    """jobs: a sequence of (src_offset, out_offset, h, w, sigma) -> the ctypes array t2o_feather_u8 takes."""
+    arr = (FeatherJob * max(len(jobs), 1))()
+    for c, (src_offset, out_offset, h, w, sigma) in zip(arr, jobs):
+        c.src_offset, c.out_offset, c.h, c.w, c.sigma = int(src_offset), int(out_offset), int(h), int(w), float(sigma)
+    return arr
+
+
+def feather_weights(sigma):
+    """The integer Gaussian of t2o_feather_u8 for `sigma`: a numpy uint16 array of R + 1 weights, centre first, with
+    w[0] + 2 * sum(w[1:]) = 65536 exactly (t2o_feather_weights; the rule is in include/t2onet_hip.h).  R = 0 -- sigma = 0 or
+    at or below about 0.2 -- is the copy, whose single weight 65536 the array holds modulo 2^16: [0]."""
+    w = np.zeros(FEATHER_MAX_RADIUS + 1, np.uint16)
+    radius = ctypes.c_int(0)
+    rc = _lib.load().t2o_feather_weights(float(sigma), w.ctypes.data, ctypes.addressof(radius))
+    replay_status(rc, 't2o_feather_weights')
+    return w[:radius.value + 1].copy()
+
+
+_feather_ws = {}
+
+
+def _feather_workspace(need, device):
+    """The intermediate of feather_u8: cached per device and stream like _scratch, but a buffer of its own -- a 24 Mpx plane
+    needs 48 MB, which the shared scratch should not be grown to."""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+    key = (device.index, _stream(device))
+    ws = _feather_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+        _feather_ws[key] = ws
+    return ws
+
+
+def feather_u8(buffer, jobs, out=None):
+    """Feather uint8 planes on the device in TWO launches, whatever their number (t2o_feather_u8): job j = (src_offset,
+    out_offset, h, w, sigma) blurs the (h, w) plane at byte src_offset of the 1-D uint8 GPU tensor `buffer` (any alignment)
+    with the exact integer separable Gaussian of standard deviation sigma <= 64 (replicated borders; feather_weights) and
+    writes it at byte out_offset of `out` -- of `buffer` itself when out is None: in place where the two offsets agree.  At
+    most 4 jobs; their destinations may not overlap each other, a source may overlap any destination.  Returns out."""
+    if not (torch.is_tensor(buffer) and buffer.is_cuda and buffer.dtype == torch.uint8 and buffer.is_contiguous()):
+        raise ValueError('feather_u8: buffer must be a contiguous uint8 GPU tensor')
+    if out is None:
+        out = buffer
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == buffer.device):
+        raise ValueError('feather_u8: out must be a contiguous uint8 GPU tensor on the buffer\'s device')
+    jobs = [tuple(j) for j in jobs]
+    if not 1 <= len(jobs) <= FEATHER_MAX_JOBS:
+        raise ValueError('feather_u8: 1 to 4 jobs per call, got %d' % len(jobs))
+    for j, (so, oo, h, w, sigma) in enumerate(jobs):
+        if not (h > 0 and w > 0):
+            continue                                             # the library refuses it
+        if not (0 <= so and so + h * w <= buffer.numel()):
+            raise ValueError('feather_u8: job %d reads outside the %d-byte buffer' % (j, buffer.numel()))
+        if not (0 <= oo and oo + h * w <= out.numel()):
+            raise ValueError('feather_u8: job %d writes outside the %d-byte output' % (j, out.numel()))
+    lib = _lib.load()
+    table = feather_jobs(jobs)
+    need = lib.t2o_feather_workspace_bytes(table, len(jobs))     # 0 for a table the library refuses: it says why below
+    ws = _feather_workspace(need, buffer.device)
+    rc = lib.t2o_feather_u8(_ptr(buffer), _ptr(out), table, len(jobs), _ptr(ws), ws.numel(), _stream(buffer.device))
+    replay_status(rc, 't2o_feather_u8')
+    return out
