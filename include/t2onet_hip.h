@@ -543,7 +543,8 @@ int t2o_lstm_layer_bwd(const float* whh, const long long* len, const float* cnew
 /* ---- image feature head: models/actor.py:50,142-143,215-216  feat = relu(bn1(vis_encoder.fc(pooled))) -- Linear(K -> D),
  * BatchNorm1d(D) in training (batch statistics over the B rows, running statistics updated as torch does: momentum,
  * unbiased variance, num_batches_tracked += 1) or evaluation mode, ReLU -- one launch (a workgroup owns 16 feature
- * columns of the whole batch, so the statistics never leave it).  B <= 64, K % 4 == 0; rows 16-byte aligned.
+ * columns of the whole batch, so the statistics never leave it).  B <= 64, K % 4 == 0, D % 4 == 0 (forward and backward
+ * alike: the backward's products read d_fc in 16-byte pieces); rows 16-byte aligned.
  * Backward: g_feat -> d_fc (gradient of the Linear's output, kept for the caller's weight-gradient product
  * d_fc^T . pooled), d_bn (2, D) = [d weight; d bias] of the batch norm, d_pooled = d_fc . fc_w (skipped when NULL). */
 typedef struct t2o_image_feature {

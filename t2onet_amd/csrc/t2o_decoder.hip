@@ -531,8 +531,8 @@ extern "C" {
 int t2o_image_feature_fwd(const t2o_image_feature_t* p, void* stream) {
   if (!p) return set_error(T2O_EINVAL, "image_feature_fwd: null argument block");
   if (!p->fc_w || !p->pooled || !p->fc_out || !p->stats || !p->feat) return set_error(T2O_EINVAL, "image_feature_fwd: null pointer");
-  if (p->B <= 0 || p->B > 64 || p->K <= 0 || p->K % 4 != 0 || p->D <= 0)
-    return set_error(T2O_EINVAL, "image_feature: need 1 <= B <= 64 (one workgroup holds a feature column of the whole batch), K % 4 == 0");
+  if (p->B <= 0 || p->B > 64 || p->K <= 0 || p->K % 4 != 0 || p->D <= 0 || p->D % 4 != 0)   // (one workgroup holds a feature column of the whole batch)
+    return set_error(T2O_EINVAL, "image_feature: need 1 <= B <= 64, K % 4 == 0, D % 4 == 0");
   if (p->training && p->B < 2) return set_error(T2O_EINVAL, "image_feature: batch statistics need more than one row");
   if (!p->training && (!p->running_mean || !p->running_var)) return set_error(T2O_EINVAL, "image_feature: evaluation mode needs the running statistics");
   if (!al16(p->pooled) || !al16(p->fc_w) || (p->pooled_copy && !al16(p->pooled_copy)))

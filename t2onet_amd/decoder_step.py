@@ -194,11 +194,14 @@ def _p(t):
 
 # ---------------------------------------------------------------------------------------------------------- feature head
 def feature_supported(pooled, fc, bn):
+    if not isinstance(bn, torch.nn.BatchNorm1d):
+        return False
+    batch_stats = bn.training or bn.running_mean is None            # (no running statistics: torch normalises with the batch's in eval() too)
+    updates = bn.training and bn.running_mean is not None
     return (pooled.is_cuda and pooled.dtype == torch.float32 and pooled.dim() == 2 and 1 <= pooled.shape[0] <= 64
             and pooled.shape[1] % 4 == 0 and fc.in_features == pooled.shape[1] and fc.out_features % 4 == 0
-            and isinstance(bn, torch.nn.BatchNorm1d) and bn.num_features == fc.out_features
-            and (bn.momentum is not None or not bn.training)
-            and ((bn.training and pooled.shape[0] > 1) or (not bn.training and bn.running_mean is not None)))
+            and bn.num_features == fc.out_features and (bn.momentum is not None or not updates)
+            and (pooled.shape[0] > 1 or not batch_stats))
 
 
 class _ImageFeatureFn(torch.autograd.Function):

@@ -536,6 +536,79 @@ def test_attention_core(dev):
         np.testing.assert_allclose(cd.grad.cpu().numpy(), c64.grad.numpy(), rtol=1e-4, atol=1e-6)
 
 
+@pytest.mark.parametrize('shape', [(3, 5, 64), (2, 9, 256), (2, 64, 1024)])
+def test_attention_backward_absent_gattn_equals_zero_gattn_bitwise(dev, shape):
+    """t2o_attn_bwd with gattn = NULL (what the decoder step passes: nothing differentiates through the weights) against
+    the same call with a zero gattn, bit for bit: k_attn_bwd (D = 64) and k_attn_bwd_wide (D = 256: 4 row groups; D = 1024:
+    one, all 64 rows)."""
+    from t2onet_amd import _lib
+    from t2onet_amd.functional import _stream
+    lib = _lib.load()
+    B, L, D = shape
+    st = _stream(dev)
+    q = synth.uniform((B, D), 91, -1, 1).to(dev)
+    ctx = synth.uniform((B, L, D), 92, -0.2, 0.2).to(dev)
+    gm = synth.uniform((B, D), 93, -1, 1).to(dev)
+    attn, mix = torch.zeros(B, L, device=dev), torch.zeros(B, D, device=dev)
+    assert lib.t2o_attn_fwd(q.data_ptr(), ctx.data_ptr(), attn.data_ptr(), mix.data_ptr(), B, L, D, st) == 0, lib.t2o_last_error()
+
+    def backward(gattn):
+        gq, gctx = torch.zeros(B, D, device=dev), torch.zeros(B, L, D, device=dev)
+        assert lib.t2o_attn_bwd(q.data_ptr(), ctx.data_ptr(), attn.data_ptr(), gm.data_ptr(), None if gattn is None else gattn.data_ptr(),
+                                gq.data_ptr(), gctx.data_ptr(), B, L, D, st) == 0, lib.t2o_last_error()
+        return gq, gctx
+
+    absent, zeros = backward(None), backward(torch.zeros(B, L, device=dev))
+    real = backward(synth.uniform((B, L), 94, -1, 1).to(dev))
+    assert float(absent[0].abs().max()) > 0.0 and float(absent[1].abs().max()) > 0.0
+    for a, z, r in zip(absent, zeros, real):
+        assert torch.equal(a, z)
+        assert not torch.equal(z, r)                       # (the argument matters: the check is not vacuous)
+
+
+@pytest.mark.parametrize('shape,single', [((4, 14, 512), False), ((3, 5, 64), False), ((4, 14, 512), True), ((3, 5, 64), True)])
+def test_attention_core_peaked_softmax(dev, shape, single):
+    """test_attention_core's comparison with q scaled until the scores span +-40 (a trained decoder: the softmax picks
+    rows); `single`: one encoder row per sample scores 150, every other weight is < 1e-30 -- in fp32 mostly 0 -- and all
+    gradients stay finite.  Tolerances: test_attention_core's, or 4 x the error of the same formula in fp32 on the CPU where
+    that is larger (per tensor, absolute)."""
+    import t2onet_amd.functional as T
+    B, L, D = shape
+    q = synth.uniform((B, D), 91, -1, 1)
+    ctx = synth.uniform((B, L, D), 92, -0.2, 0.2)
+    ctx[:, L // 2:] *= 0.0                                  # zero-padded encoder rows take part in the softmax
+    q *= 40.0 / float(torch.bmm(q.double().unsqueeze(1), ctx.double().transpose(1, 2)).abs().max())
+    if single:
+        for b in range(B):
+            ctx[b, (2 * b + 1) % L] = q[b] * (150.0 / float(q[b].double().square().sum()))
+    gm = synth.uniform((B, D), 93, -1, 1)
+    ga = synth.uniform((B, L), 94, -1, 1)
+
+    def formula(dtype):
+        qr, cr = q.clone().to(dtype).requires_grad_(True), ctx.clone().to(dtype).requires_grad_(True)
+        s = torch.bmm(qr.unsqueeze(1), cr.transpose(1, 2))
+        a = torch.softmax(s.view(-1, L), 1).view(B, 1, L)
+        mix = torch.bmm(a, cr).squeeze(1)
+        ((mix * gm.to(dtype)).sum() + (a.squeeze(1) * ga.to(dtype)).sum()).backward()
+        return s.detach(), [a.squeeze(1).detach(), mix.detach(), qr.grad, cr.grad]
+
+    s64, ref = formula(torch.float64)
+    assert 39.0 < float(s64.abs().max()) < (41.0 if not single else 151.0)
+    if single:
+        others = torch.ones(B, L, dtype=torch.bool)
+        for b in range(B):
+            others[b, (2 * b + 1) % L] = False
+        assert float(ref[0][others].max()) < 1e-30 and float(ref[0][~others].min()) > 1.0 - 1e-12
+    err32 = [float((a.double() - r).abs().max()) for a, r in zip(formula(torch.float32)[1], ref)]
+    print('fp32 CPU formula vs fp64, max abs error: attn %.2e mix %.2e d q %.2e d ctx %.2e' % tuple(err32))
+    qd, cd = q.to(dev).requires_grad_(True), ctx.to(dev).requires_grad_(True)
+    m2, a2 = T.attention_core(qd, cd)
+    ((m2 * gm.to(dev)).sum() + (a2 * ga.to(dev)).sum()).backward()
+    for got, r, e, (rtol, atol) in zip((a2, m2, qd.grad, cd.grad), ref, err32, ((1e-5, 1e-7), (1e-5, 1e-6), (1e-4, 1e-6), (1e-4, 1e-6))):
+        assert torch.isfinite(got).all()
+        np.testing.assert_allclose(got.detach().cpu().numpy(), r.numpy(), rtol=rtol, atol=max(atol, 4 * e))
+
+
 @pytest.mark.parametrize('shape', [(1, 3, 48, 40), (2, 3, 33, 70), (1, 1, 5, 7), (1, 3, 397, 600)])
 def test_ssim_kernel(dev, golden_dir, shape):
     import t2onet_amd.functional as T
@@ -577,6 +650,26 @@ def test_ssim_backward_kernel(dev, shape):
     a64b = a.double().requires_grad_(True)
     (1.0 - cpu_ref.ssim(a64b, b.double())).backward()
     np.testing.assert_allclose(x2.grad.cpu().numpy(), a64b.grad.numpy(), rtol=0, atol=1e-4 * float(a64b.grad.abs().max()))
+
+
+@pytest.mark.parametrize('shape', [(2, 3, 33, 70), (1, 1, 5, 7)])
+def test_ssim_backward_second_image_only(dev, shape):
+    """Only the second image requires a gradient (g1 = NULL in t2o_ssim_bwd; the test above has g2 = NULL only): against
+    fp64 autograd, and bit-identical to g2 of the two-sided call."""
+    import t2onet_amd.functional as T
+    B = shape[0]
+    a = synth.uniform(shape, 51)
+    b = (a + synth.uniform(shape, 52, -0.1, 0.1)).clamp(0, 1)
+    gout = synth.uniform((B,), 53, 0.5, 1.5)
+    b64 = b.double().requires_grad_(True)
+    (cpu_ref.ssim(a.double(), b64, size_average=False) * gout.double()).sum().backward()
+    x, y = a.to(dev), b.to(dev).requires_grad_(True)
+    (T.ssim(x, y, size_average=False) * gout.to(dev)).sum().backward()
+    assert x.grad is None and torch.isfinite(y.grad).all()
+    np.testing.assert_allclose(y.grad.cpu().numpy(), b64.grad.numpy(), rtol=0, atol=1e-4 * float(b64.grad.abs().max()))
+    x2, y2 = a.to(dev).requires_grad_(True), b.to(dev).requires_grad_(True)
+    (T.ssim(x2, y2, size_average=False) * gout.to(dev)).sum().backward()
+    assert torch.equal(y.grad, y2.grad) and float(x2.grad.abs().max()) > 0.0
 
 
 def test_ssim_backward_refuses_bad_arguments(dev):
