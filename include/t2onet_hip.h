@@ -201,6 +201,33 @@ int t2o_fit_multi_l1_adam(const int* ops, const int* img_index, const int* targe
                           size_t workspace_bytes, int H, int W, int steps, double lr, double beta1, double beta2,
                           double eps, int check_every, double tol, void* stream);
 
+/* ---- the two planner entry points under local-edit masks (the GIER planner: a candidate of an operator that the pair
+ * annotates a region for is fitted and scored under that region's plane).  Everything is as in the unmasked forms above
+ * -- operators, status codes, workspace, determinism, job independence, two launches per Adam iteration -- plus:
+ *   masks       (n_mask, H, W) uint8 device memory, packed with no padding: plane k starts at byte k H W (odd for odd
+ *               H W; the kernels read bytes, no alignment is assumed).  As t2o_rle_union_u8 writes them.
+ *   mask_index  HOST array like ops: -1 = no mask for job j, 0 .. n_mask - 1 = a plane; anything else is T2O_EINVAL.
+ *               masks may be NULL only when every index is -1.
+ * Forward, per pixel and channel: out = clamp01(z m + x (1 - m)), z = the operator's unclamped output, x = the input
+ * value, m = (float) of the mask byte -- a COUNT (overlapping annotated masks give 2), NOT divided by 255: what
+ * t2o_mask_select hands the episode, so a planned step replayed under the same plane gives the same picture.  The
+ * sharpness stencil reads the unmasked neighbours of the image.  Backward (the fit): g_z = sign(out - t) inv_n m, zero where
+ * the BLENDED value lies outside [0, 1]; the parameter terms are the unmasked closed forms times that g_z.
+ * A job with index -1, and a job under an all-ones plane, return the unmasked forms' numbers bit for bit (z 1 + x 0 = z
+ * for finite fp32); a call whose indices are all -1 runs the unmasked kernels themselves.  Under an all-zero plane the
+ * gradient is exactly zero and the fit returns its start values.  The workspace sizes equal the unmasked ones. */
+size_t t2o_candidates_multi_masked_workspace_bytes(int J, int C, int H, int W);
+int t2o_op_candidates_multi_l1_masked(const int* ops, const int* img_index, const int* mask_index, int J,
+                                      const float* imgs, int n_img, const unsigned char* masks, int n_mask,
+                                      const float* target, const float* params, int C, int param_stride, float* loss,
+                                      void* workspace, size_t workspace_bytes, int H, int W, void* stream);
+size_t t2o_fit_multi_masked_workspace_bytes(int J, int H, int W);
+int t2o_fit_multi_l1_adam_masked(const int* ops, const int* img_index, const int* target_index, const int* mask_index,
+                                 int J, const float* imgs, int n_img, const float* targets, int n_target,
+                                 const unsigned char* masks, int n_mask, float* params, float* dist, void* workspace,
+                                 size_t workspace_bytes, int H, int W, int steps, double lr, double beta1, double beta2,
+                                 double eps, int check_every, double tol, void* stream);
+
 /* ---- SSIM: utils/ssim/__init__.py:20-40 (forward: the evaluation metric; backward: its closed-form gradient) ----
  * 11x11 Gaussian window (sigma 1.5), zero padding, C1 = 1e-4, C2 = 9e-4.
  * out[b] = mean over (C,H,W) of the SSIM map of sample b (size_average=False of the reference;

@@ -47,6 +47,11 @@ SIGNATURES = {
     't2o_op_candidates_multi_l1': (_I, [c_i, c_i, _I, _P, _I, _P, _P, _I, _I, _P, _P, _Z, _I, _I, _P]),
     't2o_fit_multi_workspace_bytes': (_Z, [_I, _I, _I]),
     't2o_fit_multi_l1_adam': (_I, [c_i, c_i, c_i, _I, _P, _I, _P, _I, _P, _P, _P, _Z, _I, _I, _I, _D, _D, _D, _D, _I, _D, _P]),
+    't2o_candidates_multi_masked_workspace_bytes': (_Z, [_I, _I, _I, _I]),
+    't2o_op_candidates_multi_l1_masked': (_I, [c_i, c_i, c_i, _I, _P, _I, _P, _I, _P, _P, _I, _I, _P, _P, _Z, _I, _I, _P]),
+    't2o_fit_multi_masked_workspace_bytes': (_Z, [_I, _I, _I]),
+    't2o_fit_multi_l1_adam_masked': (_I, [c_i, c_i, c_i, c_i, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _Z, _I, _I, _I, _D, _D, _D, _D, _I,
+                                          _D, _P]),
     't2o_ssim_workspace_bytes': (_Z, [_I, _I, _I, _I]),
     't2o_ssim_fwd': (_I, [_P, _P, _P, _P, _Z, _I, _I, _I, _I, _P]),
     't2o_ssim_bwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

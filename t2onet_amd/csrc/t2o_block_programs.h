@@ -1299,6 +1299,44 @@ T2O_HD int cand_load(const CandArgs& a, int blk, int tid, float (&x)[3][kCandPix
   return n;     // valid pixels are the first n (px grows with i)
 }
 
+// The sweep under a local-edit mask (t2o_op_candidates_multi_l1_masked).  plane: (H,W) uint8 at ANY byte alignment, read
+// byte by byte, or null = no mask (m = 1); the values are loaded once per workgroup pass, like the pixels, and shared by
+// the candidates of the group.
+// The kCandPix bytes stay packed four to a register (8 floats would cost the masked kernel a wave of occupancy); byte i is
+// converted where it is used (one v_cvt_f32_ubyte).
+constexpr int kCandMaskWords = (kCandPix + 3) / 4;
+
+T2O_HD void cand_load_mask(const CandArgs& a, const unsigned char* plane, int blk, int tid, unsigned (&mk)[kCandMaskWords]) {
+  const unsigned hw = (unsigned)a.H * (unsigned)a.W;
+  T2O_UNROLL
+  for (int w = 0; w < kCandMaskWords; ++w) mk[w] = 0u;
+  T2O_UNROLL
+  for (int i = 0; i < kCandPix; ++i) {
+    const unsigned px = ((unsigned)blk * kCandPix + i) * kThreads + tid;
+    const unsigned v = (plane && px < hw) ? (unsigned)plane[px] : 1u;
+    mk[i >> 2] |= v << (8 * (i & 3));
+  }
+}
+
+// cand_eval with the blend out = clamp(process(x) m + x (1 - m)) in front of the L1 term (masked_l1_term, t2o_pixel_math.h)
+T2O_HD float cand_eval_masked(const CandArgs& a, const float* t, const float (&x)[3][kCandPix], const float (&tg)[3][kCandPix],
+                              const unsigned (&mk)[kCandMaskWords], int npx) {
+  float s = 0.0f;
+  for (int i = 0; i < kCandPix; ++i) {
+    if (i < npx) {
+      Rgb xi = {{x[0][i], x[1][i], x[2][i]}};
+      const Rgb r = chain_op_fwd(a.op, xi, t);
+      const float m = (float)((mk[i >> 2] >> (8 * (i & 3))) & 0xffu);
+      T2O_UNROLL
+      for (int c = 0; c < 3; ++c) {
+        float gz;
+        s += masked_l1_term(r.c[c], xi.c[c], m, tg[c][i], 0.0f, gz);
+      }
+    }
+  }
+  return s;
+}
+
 // ===================================================================== sequence planning (host)
 // A sequence is cut into segments: maximal runs of pointwise operators (<= kMaxChain) that one
 // fused kernel pair handles, and single sharpness operators (stencil kernels).  Identity (-1)

@@ -11,6 +11,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/t2onet_hip.h"
 #include "t2o_block_programs.h"
 #include "t2o_chain_kernels.h"
@@ -666,7 +668,16 @@ struct MultiCandArgs {
   int C, param_stride, H, W, nblk;
 };
 
-__global__ __launch_bounds__(kThreads) void k_candidates_multi_l1(MultiCandArgs m) {
+// the masked form's arguments: job j blends every candidate with planes (n_mask, H, W) uint8, packed -- plane k starts at
+// byte k H W, any alignment, read byte by byte -- under mask_index[j]; -1 = no mask (m = 1).  The unmasked kernel keeps
+// MultiCandArgs as its argument, so its code does not change.
+struct MultiCandMaskArgs : MultiCandArgs {
+  const unsigned char* masks;
+  int mask_index[kMaxCandJobs];
+};
+
+template <bool MASKED>
+__global__ __launch_bounds__(kThreads) void k_candidates_multi_l1(typename std::conditional<MASKED, MultiCandMaskArgs, MultiCandArgs>::type m) {
   __shared__ float tab[kCandPerBlock * kTabStride];
   __shared__ float wsum[kCandPerBlock][kThreads / 64];
   const int job = blockIdx.y;
@@ -682,10 +693,18 @@ __global__ __launch_bounds__(kThreads) void k_candidates_multi_l1(MultiCandArgs 
     cand_build_table(a, c0 + threadIdx.x, tab + threadIdx.x * kTabStride);
   float x[3][kCandPix], tg[3][kCandPix];
   const int npx = cand_load(a, blk, threadIdx.x, x, tg);
+  unsigned mk[kCandMaskWords];                                             // the mask bytes of this thread's pixels: read once,
+  if constexpr (MASKED) {                                                  // shared by the group's candidates like x and tg
+    const int k = m.mask_index[job];
+    cand_load_mask(a, k >= 0 ? m.masks + (size_t)k * m.H * m.W : nullptr, blk, threadIdx.x, mk);
+  }
   __syncthreads();
   for (int j = 0; j < kCandPerBlock; ++j) {
     if (c0 + j >= a.C) break;
-    const float s = wave_sum(cand_eval(a, tab + j * kTabStride, x, tg, npx));
+    float v;
+    if constexpr (MASKED) v = cand_eval_masked(a, tab + j * kTabStride, x, tg, mk, npx);
+    else v = cand_eval(a, tab + j * kTabStride, x, tg, npx);
+    const float s = wave_sum(v);
     if ((threadIdx.x & 63) == 0) wsum[j][threadIdx.x >> 6] = s;
   }
   __syncthreads();
@@ -1652,15 +1671,24 @@ size_t t2o_candidates_multi_workspace_bytes(int J, int C, int H, int W) {
   return (size_t)J * t2o_candidates_workspace_bytes(C, H, W);
 }
 
-int t2o_op_candidates_multi_l1(const int* ops, const int* img_index, int J, const float* imgs, int n_img, const float* target,
-                               const float* params, int C, int param_stride, float* loss, void* workspace,
-                               size_t workspace_bytes, int H, int W, void* stream) {
-  if (!ops || !img_index || !imgs || !target || !params || !loss) return fail(T2O_EINVAL, "candidates_multi_l1: null pointer");
+}  // extern "C"
+
+// masked_entry = false: t2o_op_candidates_multi_l1.  true: the masked entry point; a call whose indices are all -1 runs
+// the unmasked kernel (the same numbers: m = 1 is exact), any other the masked instantiation.
+static int candidates_multi_impl(const int* ops, const int* img_index, const int* mask_index, bool masked_entry, int J,
+                                 const float* imgs, int n_img, const unsigned char* masks, int n_mask, const float* target,
+                                 const float* params, int C, int param_stride, float* loss, void* workspace,
+                                 size_t workspace_bytes, int H, int W, void* stream) {
+  if (!ops || !img_index || !imgs || !target || !params || !loss || (masked_entry && !mask_index))
+    return fail(T2O_EINVAL, "candidates_multi_l1: null pointer");
   if (J <= 0 || J > kMaxCandJobs) return fail(T2O_EINVAL, "candidates_multi_l1: 1 <= J <= 64 jobs per launch");
   if (C <= 0 || H <= 0 || W <= 0 || n_img <= 0) return fail(T2O_EINVAL, "C, H, W, n_img must be positive");
+  if (masked_entry && n_mask < 0) return fail(T2O_EINVAL, "candidates_multi_l1: n_mask < 0");
+  if (masked_entry && (size_t)H * W > 0x7fffffffull / 3) return fail(T2O_EINVAL, "candidates_multi_l1: image too large");
   if (!workspace || workspace_bytes < t2o_candidates_multi_workspace_bytes(J, C, H, W)) return fail(T2O_EWORKSPACE, "workspace too small");
-  MultiCandArgs m;
+  MultiCandMaskArgs m;
   memset(&m, 0, sizeof(m));
+  bool any_mask = false;
   for (int j = 0; j < J; ++j) {
     const int op = ops[j];
     if (op == OP_SHARPNESS || op == OP_IDENTITY || !op_supported(op))
@@ -1669,15 +1697,46 @@ int t2o_op_candidates_multi_l1(const int* ops, const int* img_index, int J, cons
     if (img_index[j] < 0 || img_index[j] >= n_img) return fail(T2O_EINVAL, "img_index out of range");
     m.op[j] = op;
     m.img_index[j] = img_index[j];
+    m.mask_index[j] = -1;
+    if (masked_entry) {
+      const int mk = mask_index[j];
+      if (mk < -1 || mk >= n_mask) return fail(T2O_EINVAL, "mask_index out of range (-1 = no mask, 0 .. n_mask - 1)");
+      if (mk >= 0 && !masks) return fail(T2O_EINVAL, "candidates_multi_l1: null pointer (masks) with a mask_index >= 0");
+      m.mask_index[j] = mk;
+      any_mask = any_mask || mk >= 0;
+    }
   }
-  m.imgs = imgs; m.target = target; m.params = params; m.partials = (float*)workspace;
+  m.imgs = imgs; m.target = target; m.params = params; m.partials = (float*)workspace; m.masks = masks;
   m.C = C; m.param_stride = param_stride; m.H = H; m.W = W;
   m.nblk = (int)(((size_t)H * W + (size_t)kThreads * kCandPix - 1) / ((size_t)kThreads * kCandPix));
   const unsigned groups = (unsigned)((C + kCandPerBlock - 1) / kCandPerBlock);
   hipStream_t st = (hipStream_t)stream;
-  k_candidates_multi_l1<<<dim3((unsigned)m.nblk * groups, (unsigned)J), kThreads, 0, st>>>(m);
+  const dim3 grid((unsigned)m.nblk * groups, (unsigned)J);
+  if (any_mask) k_candidates_multi_l1<true><<<grid, kThreads, 0, st>>>(m);
+  else k_candidates_multi_l1<false><<<grid, kThreads, 0, st>>>(m);
   k_candidates_finalize<<<(unsigned)(J * C), 64, 0, st>>>(m.partials, m.nblk, 1.0f / (3.0f * (float)H * (float)W), loss);
   return check_launch("candidate sweep (multi)");
+}
+
+extern "C" {
+
+int t2o_op_candidates_multi_l1(const int* ops, const int* img_index, int J, const float* imgs, int n_img, const float* target,
+                               const float* params, int C, int param_stride, float* loss, void* workspace,
+                               size_t workspace_bytes, int H, int W, void* stream) {
+  return candidates_multi_impl(ops, img_index, nullptr, false, J, imgs, n_img, nullptr, 0, target, params, C, param_stride, loss,
+                               workspace, workspace_bytes, H, W, stream);
+}
+
+size_t t2o_candidates_multi_masked_workspace_bytes(int J, int C, int H, int W) {
+  return t2o_candidates_multi_workspace_bytes(J, C, H, W);
+}
+
+int t2o_op_candidates_multi_l1_masked(const int* ops, const int* img_index, const int* mask_index, int J, const float* imgs,
+                                      int n_img, const unsigned char* masks, int n_mask, const float* target, const float* params,
+                                      int C, int param_stride, float* loss, void* workspace, size_t workspace_bytes, int H,
+                                      int W, void* stream) {
+  return candidates_multi_impl(ops, img_index, mask_index, true, J, imgs, n_img, masks, n_mask, target, params, C, param_stride,
+                               loss, workspace, workspace_bytes, H, W, stream);
 }
 
 size_t t2o_ssim_workspace_bytes(int B, int C, int H, int W) {

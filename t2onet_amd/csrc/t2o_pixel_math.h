@@ -277,6 +277,22 @@ T2O_HD float sharp_delta(float c, float up, float left, float right, float down)
 // Operator.execute epilogue: blend with the mask, clamp.  z is the pre-clamp value.
 T2O_HD float blend(float o, float x, float m) { return o * m + x * (1.0f - m); }
 
+// The planner's per-pixel-channel L1 term under a local-edit mask (t2o_op_candidates_multi_l1_masked,
+// t2o_fit_multi_l1_adam_masked): z = the operator's unclamped output, x = the input value, m = (float) of the mask byte --
+// a COUNT, 0, 1, 2, ..., not divided by 255 --, t = the target value.
+//   out = clamp01(z m + x (1 - m));  returns |out - t|;
+//   gz  = d (inv_n |out - t|) / d z = sign(out - t) inv_n m, zero where the BLENDED value lies outside [0, 1]
+//         (clamp backward, inclusive like PyTorch's).
+// With m == 1 the blend is z 1 + x 0 = z for finite fp32, so value and gz are those of the unmasked kernels bit for bit.
+T2O_HD float l1_sign(float d) { return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f); }
+
+T2O_HD float masked_l1_term(float z, float x, float m, float t, float inv_n, float& gz) {
+  const float b = blend(z, x, m);
+  const float diff = clamp01(b) - t;
+  gz = (b >= 0.0f && b <= 1.0f) ? (l1_sign(diff) * inv_n) * m : 0.0f;
+  return fabsf(diff);
+}
+
 // Pointwise dispatcher (everything except sharpness / identity).
 T2O_HD Rgb pointwise_fwd(int op, const Rgb& x, const float* p, const Curve& cv) {
   switch (op) {

@@ -5,6 +5,7 @@
 // with two launches per iteration and no host synchronisation:
 //   k_fit_eval<true>   grid (pixel chunks, jobs): forward, L1 sign, closed-form parameter derivative of every pixel;
 //                      one partial sum per (job, slot, chunk), written -- never accumulated -- to the workspace
+//                      (k_fit_eval<GRAD, true>: the same under a per-job local-edit mask plane, see FitMaskArgs)
 //   k_fit_adam         one wave per job: the chunk partials summed in index order, the curve raw sums turned into
 //                      gradients, torch.optim.Adam's update, and the stop rule of the serial fit evaluated per job
 // and a closing k_fit_eval<false> + k_fit_dist pair that leaves the loss at the returned parameters.
@@ -16,6 +17,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "t2o_pixel_math.h"
 #include "t2onet_hip.h"
@@ -48,6 +50,14 @@ struct FitArgs {
   float inv_n;            // 1 / (3 H W)
 };
 
+// The masked form's arguments: job j blends its operator with planes (n_mask, H, W) uint8, packed -- plane k starts at
+// byte k H W, any alignment, read byte by byte -- under mask_index[j]; -1 = no mask (m = 1).  The unmasked kernels keep
+// FitArgs as their argument, so their code does not change.
+struct FitMaskArgs : FitArgs {
+  const unsigned char* masks;
+  int mask_index[kFitMaxJobs];
+};
+
 __device__ __forceinline__ double wave_sum_f64(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);     // fixed butterfly: the same order every run
   return v;
@@ -60,8 +70,8 @@ __device__ __forceinline__ float fit_at(const float* plane, int y, int x, int H,
   return (y >= 0 && y < H && x >= 0 && x < W) ? plane[(size_t)y * W + x] : 0.0f;
 }
 
-template <bool GRAD>
-__global__ __launch_bounds__(kFitThreads) void k_fit_eval(FitArgs a) {
+template <bool GRAD, bool MASKED>
+__global__ __launch_bounds__(kFitThreads) void k_fit_eval(typename std::conditional<MASKED, FitMaskArgs, FitArgs>::type a) {
   __shared__ double wsum[kFitSlots][kFitThreads / 64];
   const int job = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
   if (GRAD && (a.flags[job] & kFitFrozen)) return;                         // (uniform over the workgroup)
@@ -70,6 +80,10 @@ __global__ __launch_bounds__(kFitThreads) void k_fit_eval(FitArgs a) {
   const float* img = a.imgs + (size_t)a.img_index[job] * 3 * hw;
   const float* tgt = a.targets + (size_t)a.target_index[job] * 3 * hw;
   const float* prow = a.params + (size_t)job * kMaxParam;
+  const unsigned char* mplane = nullptr;                                   // (uniform; stays null for a job without a mask)
+  if constexpr (MASKED) {
+    if (a.mask_index[job] >= 0) mplane = a.masks + (size_t)a.mask_index[job] * hw;
+  }
   const bool curve = op == OP_COLOR || op == OP_TONE;
   Curve cv = {};
   if (curve) curve_load(cv, prow, op == OP_COLOR);
@@ -99,12 +113,18 @@ __global__ __launch_bounds__(kFitThreads) void k_fit_eval(FitArgs a) {
       z = pointwise_fwd(op, x, p0, cv);
     }
     Rgb go;
-    T2O_UNROLL
-    for (int c = 0; c < 3; ++c) {
-      const float diff = clamp01(z.c[c]) - t[c];
-      loss += fabsf(diff);
-      const float gz = fit_sign(diff) * a.inv_n;
-      go.c[c] = (z.c[c] >= 0.0f && z.c[c] <= 1.0f) ? gz : 0.0f;           // clamp(0,1) backward, inclusive
+    if constexpr (MASKED) {
+      const float m = mplane ? (float)mplane[px] : 1.0f;                   // one byte per pixel, shared by the three channels
+      T2O_UNROLL
+      for (int c = 0; c < 3; ++c) loss += masked_l1_term(z.c[c], x.c[c], m, t[c], a.inv_n, go.c[c]);
+    } else {
+      T2O_UNROLL
+      for (int c = 0; c < 3; ++c) {
+        const float diff = clamp01(z.c[c]) - t[c];
+        loss += fabsf(diff);
+        const float gz = fit_sign(diff) * a.inv_n;
+        go.c[c] = (z.c[c] >= 0.0f && z.c[c] <= 1.0f) ? gz : 0.0f;         // clamp(0,1) backward, inclusive
+      }
     }
     if (!GRAD) continue;
     if (op == OP_SHARPNESS) {
@@ -214,10 +234,17 @@ size_t t2o_fit_multi_workspace_bytes(int J, int H, int W) {
   return (size_t)J * ((size_t)kFitSlots * fit_nblk(H, W) * sizeof(double) + (size_t)kFitStateWords * sizeof(float));
 }
 
-int t2o_fit_multi_l1_adam(const int* ops, const int* img_index, const int* target_index, int J, const float* imgs, int n_img,
-                          const float* targets, int n_target, float* params, float* dist, void* workspace,
-                          size_t workspace_bytes, int H, int W, int steps, double lr, double beta1, double beta2, double eps,
-                          int check_every, double tol, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// mask_index == nullptr: the unmasked entry point.  Otherwise the masked one; a call whose indices are all -1 runs the
+// unmasked kernels (the same numbers: m = 1 is exact), any other the masked instantiation.
+int fit_multi_impl(const int* ops, const int* img_index, const int* target_index, const int* mask_index, bool masked_entry, int J,
+                   const float* imgs, int n_img, const float* targets, int n_target, const unsigned char* masks, int n_mask,
+                   float* params, float* dist, void* workspace, size_t workspace_bytes, int H, int W, int steps, double lr,
+                   double beta1, double beta2, double eps, int check_every, double tol, void* stream) {
+  if (masked_entry && !mask_index) return set_error(T2O_EINVAL, "fit_multi_l1_adam: null pointer");
   if (!ops || !img_index || !target_index || !imgs || !targets || !params || !dist)
     return set_error(T2O_EINVAL, "fit_multi_l1_adam: null pointer");
   if (J <= 0 || J > kFitMaxJobs) return set_error(T2O_EINVAL, "fit_multi_l1_adam: 1 <= J <= 64 jobs per call");
@@ -226,8 +253,10 @@ int t2o_fit_multi_l1_adam(const int* ops, const int* img_index, const int* targe
   if (steps < 0) return set_error(T2O_EINVAL, "fit_multi_l1_adam: steps < 0");
   if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
     return set_error(T2O_EINVAL, "fit_multi_l1_adam: betas must lie in [0, 1)");
-  FitArgs a;
+  if (masked_entry && n_mask < 0) return set_error(T2O_EINVAL, "fit_multi_l1_adam: n_mask < 0");
+  FitMaskArgs a;
   memset(&a, 0, sizeof(a));
+  bool any_mask = false;
   for (int j = 0; j < J; ++j) {
     const int op = ops[j];
     if (!(op == OP_BRIGHTNESS || op == OP_CONTRAST || op == OP_SATURATION || op == OP_COLOR || op == OP_TONE || op == OP_SHARPNESS))
@@ -237,10 +266,18 @@ int t2o_fit_multi_l1_adam(const int* ops, const int* img_index, const int* targe
     a.op[j] = op;
     a.img_index[j] = img_index[j];
     a.target_index[j] = target_index[j];
+    a.mask_index[j] = -1;
+    if (masked_entry) {
+      const int mk = mask_index[j];
+      if (mk < -1 || mk >= n_mask) return set_error(T2O_EINVAL, "fit_multi_l1_adam: mask_index out of range (-1 = no mask, 0 .. n_mask - 1)");
+      if (mk >= 0 && !masks) return set_error(T2O_EINVAL, "fit_multi_l1_adam: null pointer (masks) with a mask_index >= 0");
+      a.mask_index[j] = mk;
+      any_mask = any_mask || mk >= 0;
+    }
   }
   if (!workspace || workspace_bytes < t2o_fit_multi_workspace_bytes(J, H, W)) return set_error(T2O_EWORKSPACE, "fit_multi_l1_adam: workspace too small");
   if ((size_t)workspace & 7) return set_error(T2O_EINVAL, "fit_multi_l1_adam: workspace must be 8-byte aligned");
-  a.imgs = imgs; a.targets = targets; a.params = params;
+  a.imgs = imgs; a.targets = targets; a.params = params; a.masks = masks;
   a.H = H; a.W = W; a.nblk = fit_nblk(H, W);
   a.inv_n = 1.0f / (3.0f * (float)H * (float)W);
   a.partials = (double*)workspace;
@@ -254,13 +291,38 @@ int t2o_fit_multi_l1_adam(const int* ops, const int* img_index, const int* targe
   k_fit_init<<<1, 256, 0, st>>>((unsigned*)state, J * kFitStateWords);
   for (int t = 1; t <= steps; ++t) {
     const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
-    k_fit_eval<true><<<grid, kFitThreads, 0, st>>>(a);
+    if (any_mask) k_fit_eval<true, true><<<grid, kFitThreads, 0, st>>>(a);
+    else k_fit_eval<true, false><<<grid, kFitThreads, 0, st>>>(a);
     k_fit_adam<<<(unsigned)J, 64, 0, st>>>(a, (float)(lr / bc1), (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)sqrt(bc2),
                                            (float)eps, (check_every > 0 && t % check_every == 0) ? 1 : 0, (float)tol);
   }
-  k_fit_eval<false><<<grid, kFitThreads, 0, st>>>(a);
+  if (any_mask) k_fit_eval<false, true><<<grid, kFitThreads, 0, st>>>(a);
+  else k_fit_eval<false, false><<<grid, kFitThreads, 0, st>>>(a);
   k_fit_dist<<<(unsigned)J, 64, 0, st>>>(a, dist);
   return hipGetLastError() == hipSuccess ? T2O_OK : set_error(T2O_ELAUNCH, "fit_multi_l1_adam launch failed");
+}
+
+}  // namespace
+
+extern "C" {
+
+int t2o_fit_multi_l1_adam(const int* ops, const int* img_index, const int* target_index, int J, const float* imgs, int n_img,
+                          const float* targets, int n_target, float* params, float* dist, void* workspace,
+                          size_t workspace_bytes, int H, int W, int steps, double lr, double beta1, double beta2, double eps,
+                          int check_every, double tol, void* stream) {
+  return fit_multi_impl(ops, img_index, target_index, nullptr, false, J, imgs, n_img, targets, n_target, nullptr, 0, params, dist,
+                        workspace, workspace_bytes, H, W, steps, lr, beta1, beta2, eps, check_every, tol, stream);
+}
+
+size_t t2o_fit_multi_masked_workspace_bytes(int J, int H, int W) { return t2o_fit_multi_workspace_bytes(J, H, W); }
+
+int t2o_fit_multi_l1_adam_masked(const int* ops, const int* img_index, const int* target_index, const int* mask_index, int J,
+                                 const float* imgs, int n_img, const float* targets, int n_target, const unsigned char* masks,
+                                 int n_mask, float* params, float* dist, void* workspace, size_t workspace_bytes, int H, int W,
+                                 int steps, double lr, double beta1, double beta2, double eps, int check_every, double tol,
+                                 void* stream) {
+  return fit_multi_impl(ops, img_index, target_index, mask_index, true, J, imgs, n_img, targets, n_target, masks, n_mask, params,
+                        dist, workspace, workspace_bytes, H, W, steps, lr, beta1, beta2, eps, check_every, tol, stream);
 }
 
 }  // extern "C"

@@ -960,9 +960,33 @@ def fused_sequence_l1_value_grad(img, ops, params, target, gloss=None, want_imag
     return loss, gimg, gparams, (out if want_image else None)
 
 
-def candidates_multi_l1(ops, img_index, imgs, target, params):
+def _planner_masks(lib, who, masks, mask_index, J, imgs):
+    """The (masks, mask_index) keywords of the two planner calls, checked HERE so that a wrong plane or index is a Python
+    error and never a GPU fault -> (planes or None, n_mask, ctypes index array)."""
+    for name in ('t2o_op_candidates_multi_l1_masked', 't2o_fit_multi_l1_adam_masked'):
+        if not hasattr(lib, name):
+            raise RuntimeError('%s: libt2onet_hip.so has no %s (a library without the masked planner kernels)' % (who, name))
+    index = [-1] * J if mask_index is None else [int(k) for k in mask_index]
+    if len(index) != J:
+        raise ValueError('%s: one mask index per job (%d for %d jobs)' % (who, len(index), J))
+    n = 0
+    if masks is not None:
+        if not (torch.is_tensor(masks) and masks.is_cuda and masks.dtype == torch.uint8 and masks.dim() == 3 and masks.is_contiguous()):
+            raise ValueError('%s: masks must be a contiguous (N,H,W) uint8 GPU tensor' % who)
+        if masks.device != imgs.device or tuple(masks.shape[-2:]) != tuple(imgs.shape[-2:]):
+            raise ValueError('%s: masks %s on %s do not match the images %s on %s' % (
+                who, tuple(masks.shape), masks.device, tuple(imgs.shape), imgs.device))
+        n = masks.shape[0]
+    if any(k < -1 or k >= n for k in index):
+        raise ValueError('%s: mask_index must lie in [-1, %d) (-1 = no mask), got %s' % (who, n, index))
+    return (masks if n else None), n, (ctypes.c_int * max(J, 1))(*index)
+
+
+def candidates_multi_l1(ops, img_index, imgs, target, params, masks=None, mask_index=None):
     """loss[j, c] = mean |execute(imgs[img_index[j]], ops[j], params[j, c]) - target| for J jobs x C candidates in
-    ONE launch (t2o_op_candidates_multi_l1).  ops / img_index: python ints; imgs (n,3,H,W); params (J,C,n)."""
+    ONE launch (t2o_op_candidates_multi_l1).  ops / img_index: python ints; imgs (n,3,H,W); params (J,C,n).
+    masks (N,H,W) uint8 on the images' device + mask_index (python ints, -1 = none): job j's candidates are blended under
+    plane mask_index[j], m = float(byte) -- execute(..., mask=plane.float()) -- by t2o_op_candidates_multi_l1_masked."""
     _need_gpu(imgs, target, params)
     imgs = imgs.reshape(-1, 3, *imgs.shape[-2:]).contiguous()
     target = target.reshape(3, *target.shape[-2:]).contiguous()
@@ -970,10 +994,18 @@ def candidates_multi_l1(ops, img_index, imgs, target, params):
     J, C = params.shape[0], params.shape[1]
     H, W = imgs.shape[-2:]
     lib = _lib.load()
+    if masks is not None or mask_index is not None:
+        planes, n_mask, c_mask = _planner_masks(lib, 'candidates_multi_l1', masks, mask_index, J, imgs)
     loss = torch.empty(J, C, dtype=torch.float32, device=imgs.device)
     ws = torch.empty(max(lib.t2o_candidates_multi_workspace_bytes(J, C, H, W), 4), dtype=torch.uint8, device=imgs.device)
     c_ops = (ctypes.c_int * J)(*[int(o) for o in ops])
     c_idx = (ctypes.c_int * J)(*[int(i) for i in img_index])
+    if masks is not None or mask_index is not None:
+        rc = lib.t2o_op_candidates_multi_l1_masked(c_ops, c_idx, c_mask, J, _ptr(imgs), imgs.shape[0], _ptr(planes), n_mask,
+                                                   _ptr(target), _ptr(params), C, params.shape[2], _ptr(loss), _ptr(ws),
+                                                   ws.numel(), H, W, _stream(imgs.device))
+        _lib.check(rc, 't2o_op_candidates_multi_l1_masked')
+        return loss
     rc = lib.t2o_op_candidates_multi_l1(c_ops, c_idx, J, _ptr(imgs), imgs.shape[0], _ptr(target), _ptr(params), C,
                                         params.shape[2], _ptr(loss), _ptr(ws), ws.numel(), H, W, _stream(imgs.device))
     _lib.check(rc, 't2o_op_candidates_multi_l1')
@@ -984,8 +1016,9 @@ FIT_MAX_JOBS = 64
 
 
 def fit_multi_l1(ops, img_index, imgs, targets, target_index, params0, steps=300, lr=2e-2, check_every=50, tol=1e-6,
-                 betas=(0.9, 0.999), eps=1e-8):
-    """Adam on the parameters of J <= 64 jobs at once, entirely on the device (t2o_fit_multi_l1_adam): job j fits
+                 betas=(0.9, 0.999), eps=1e-8, masks=None, mask_index=None):
+    """Adam on the parameters of J <= 64 jobs at once, entirely on the device (t2o_fit_multi_l1_adam; with masks (N,H,W)
+    uint8 + mask_index, as in candidates_multi_l1, t2o_fit_multi_l1_adam_masked: job j is fitted under its plane): job j fits
     operator ops[j] on imgs[img_index[j]] against targets[target_index[j]] under mean |execute - target|, starting
     from params0[j].  ops / img_index / target_index: python ints; imgs (n,3,H,W); targets (m,3,H,W); params0 (J,n<=24).
     torch.optim.Adam's update and the serial fit's stop rule (check_every <= 0: none), two launches per iteration, no
@@ -1011,6 +1044,14 @@ def fit_multi_l1(ops, img_index, imgs, targets, target_index, params0, steps=300
     c_ops = (ctypes.c_int * max(J, 1))(*[int(o) for o in ops])
     c_img = (ctypes.c_int * max(J, 1))(*[int(i) for i in img_index])
     c_tgt = (ctypes.c_int * max(J, 1))(*[int(i) for i in target_index])
+    if masks is not None or mask_index is not None:
+        planes, n_mask, c_mask = _planner_masks(lib, 'fit_multi_l1', masks, mask_index, J, imgs)
+        rc = lib.t2o_fit_multi_l1_adam_masked(c_ops, c_img, c_tgt, c_mask, J, _ptr(imgs), imgs.shape[0], _ptr(targets),
+                                              targets.shape[0], _ptr(planes), n_mask, _ptr(params), _ptr(dist), _ptr(ws),
+                                              ws.numel(), H, W, int(steps), float(lr), float(betas[0]), float(betas[1]),
+                                              float(eps), int(check_every), float(tol), _stream(dev))
+        _lib.check(rc, 't2o_fit_multi_l1_adam_masked')
+        return params, dist
     rc = lib.t2o_fit_multi_l1_adam(c_ops, c_img, c_tgt, J, _ptr(imgs), imgs.shape[0], _ptr(targets), targets.shape[0],
                                    _ptr(params), _ptr(dist), _ptr(ws), ws.numel(), H, W, int(steps), float(lr),
                                    float(betas[0]), float(betas[1]), float(eps), int(check_every), float(tol), _stream(dev))
