@@ -894,6 +894,25 @@ int t2o_rle_union_u8(const void* host_tables, const void* dev_tables, int n_jobs
 int t2o_mask_select(const unsigned char* planes, const int* slot, const long long* pred_op, float* out, int N, int B, int V,
                     int H, int W, void* stream);
 
+/* ---- per-sample operators under the uint8 mask planes (t2o_apply_planes.hip): t2o_mask_select + t2o_apply_fwd / _bwd
+ * (mask_ch = 1) as ONE call that reads the planes where they lie.  For sample b the mask is m = float(planes[k][y][x]) with
+ * k = slot[b * V + pred_op[b]], and m = 1 everywhere when pred_op[b] lies outside [0, V) or k is not a plane number
+ * (outside [0, N)): t2o_mask_select's rule.  m is a COUNT (0, 1, 2, ...), not divided by 255.  Then exactly t2o_apply_*:
+ * out = clamp(process(x) * m + x * (1 - m), 0, 1), op_id[b] the executor index (-1 = identity, returned as is), sharpness
+ * reads unmasked neighbours; param rows of >= 24 floats.  No (B,1,H,W) fp32 mask exists anywhere: the forward moves 25
+ * bytes per pixel instead of 33 and the backward keeps nothing but img, param and the ids.
+ * planes: (N,H,W) uint8, packed (plane k starts at byte k * H * W: no alignment is assumed), NULL only when N = 0;
+ * slot: (B,V) int32; pred_op: (B) int64; any H, W >= 1.  gimg may be NULL; workspace: t2o_workspace_bytes(B, H, W).
+ * out, gimg and gparam are BIT-IDENTICAL to t2o_mask_select followed by t2o_apply_fwd / t2o_apply_bwd: the same per-pixel
+ * programs with only the mask fetch replaced, the same launch geometry, partial-sum layout and finalisation kernel.
+ * T2O_EINVAL: null pointers (planes with N > 0), N < 0, B, V, H or W not positive, H * W >= 2^31, strides below 24;
+ * T2O_EWORKSPACE: workspace null or too small.  Enqueue only: no allocation, no synchronisation, capturable, deterministic. */
+int t2o_apply_planes_fwd(const int* op_id, const long long* pred_op, const unsigned char* planes, const int* slot, int N, int V,
+                         const float* img, const float* param, int param_stride, float* out, int B, int H, int W, void* stream);
+int t2o_apply_planes_bwd(const int* op_id, const long long* pred_op, const unsigned char* planes, const int* slot, int N, int V,
+                         const float* img, const float* param, int param_stride, const float* gout, float* gimg, float* gparam,
+                         int gparam_stride, void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,8 @@ SIGNATURES = {
     't2o_end_select_var_mean': (_I, [_P, _P, _I, _I, _I, _Z, _P, _P, _Z, _P]),
     't2o_rle_union_u8': (_I, [_P, _P, _I, _I, _I, ctypes.c_longlong, _P, ctypes.c_longlong, _P]),
     't2o_mask_select': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    't2o_apply_planes_fwd': (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _I, _I, _I, _P]),
+    't2o_apply_planes_bwd': (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _Z, _I, _I, _I, _P]),
 }
 
 

@@ -138,13 +138,22 @@ class Actor(nn.Module):
             masks.append(torch.ones_like(img[i]) if mask is None else mask)
         return torch.stack(masks, dim=0)
 
-    def step_mask(self, img, mask_dict, pred_op):
+    @staticmethod
+    def _is_table(mask_dict):
+        return hasattr(mask_dict, 'planes') and hasattr(mask_dict, 'slot')
+
+    def step_mask(self, img, mask_dict, pred_op, fuse=False):
         """The mask of one decoding step.  A gier.MaskTable: ONE functional.mask_select on the device-resident pred_op ->
-        (B,1,H,W), no host read and no loop over samples.  A list of dicts: get_gt_mask -> (B,3,H,W), one host read."""
-        if hasattr(mask_dict, 'planes') and hasattr(mask_dict, 'slot'):
+        (B,1,H,W), no host read and no loop over samples -- or, fuse=True, no launch at all: a functional.PlaneMask that
+        the operator kernels read in place (functional.apply_planes).  A list of dicts: get_gt_mask -> (B,3,H,W), one host
+        read."""
+        if self._is_table(mask_dict):
             if tuple(mask_dict.size) != tuple(img.shape[-2:]) or mask_dict.slot.shape[0] != img.shape[0]:
                 raise ValueError('MaskTable of %d samples at %s for images %s' % (mask_dict.slot.shape[0], mask_dict.size, tuple(img.shape)))
-            return T.mask_select(mask_dict.planes, mask_dict.slot, pred_op.detach())
+            pred_op = pred_op.detach().reshape(-1).contiguous()         # (a column of the teacher's y is strided)
+            if fuse:
+                return T.PlaneMask(mask_dict.planes, mask_dict.slot, pred_op)
+            return T.mask_select(mask_dict.planes, mask_dict.slot, pred_op)
         return self.get_gt_mask(img, mask_dict, pred_op.detach().cpu().numpy())
 
     def divide_op_group(self, ops):
@@ -184,7 +193,7 @@ class Actor(nn.Module):
         return self.executor.execute_per_sample(img, ops_vocab.view(-1) - 3 if exec_op is None else exec_op, mask, features=context)
 
     # ------------------------------------------------------------------ teacher forcing
-    def supervised_forward(self, x, y, img_x, img_y, gt_params, mask, lengths=None):
+    def supervised_forward(self, x, y, img_x, img_y, gt_params, mask, lengths=None, fuse_masks=False):
         """actor.py:116-181.  Returns (pred_imgs (B,step-2,3,H,W), pred_params (B,step-2,24),
         pred_logprobs (B,step-1,n_cls)).
 
@@ -192,7 +201,12 @@ class Actor(nn.Module):
         one per executed step: step i blends with mask[:, i-1].  The reference unpacks a 5-D mask the same way
         (actor.py:136-137) but then hands the WHOLE 5-D tensor to every operator, which only broadcasts for one
         sample and one masked step; in that case both give the same images (golden `sup_mask_*`).  Anything
-        that is not 5-D fails the reference's unpack and is rejected here too."""
+        that is not 5-D fails the reference's unpack and is rejected here too.
+        Also a gier.MaskTable: step i blends with the plane of the operator it executes, y[:, i] -- one mask_select per
+        step, or with fuse_masks=True none (the operator kernels read the planes: functional.apply_planes, same bits)."""
+        table = mask if self._is_table(mask) else None
+        if table is not None:
+            mask = None
         if mask is not None:
             if mask.dim() != 5 or mask.shape[0] != x.shape[0] or mask.shape[2] not in (1, 3):
                 raise ValueError('mask must be (bs, n_steps, 1|3, h, w), got %s' % (tuple(mask.shape),))
@@ -210,25 +224,30 @@ class Actor(nn.Module):
             ops = y[:, i].unsqueeze(-1)
             if i == step - 1:
                 break
-            out, par = self._execute(img_x, ops, context, None if mask is None else mask[:, i - 1])
+            step_mask = self.step_mask(img_x, table, ops, fuse_masks) if table is not None else (None if mask is None else mask[:, i - 1])
+            out, par = self._execute(img_x, ops, context, step_mask)
             pred_imgs.append(out)
             pred_params.append(par)
             img_x = img_y[:, i - 1]                        # next input = planned ground-truth intermediate
         return torch.stack(pred_imgs, 1), torch.stack(pred_params, 1), torch.cat(logprobs, 1)
 
     # ------------------------------------------------------------------ free running
-    def episode_forward(self, x, img_x, mask_dict, reinforce_sample=1, lengths=None, longest=None, stack=True):
+    def episode_forward(self, x, img_x, mask_dict, reinforce_sample=1, lengths=None, longest=None, stack=True, fuse_masks=False):
         """actor.py:184-284.  Returns (state, pred_imgs (B,T,3,H,W), pred_ops (B,T), pred_params list of T (B,24)).
         lengths / longest: see RNNEncoder.forward (host-side lengths save a synchronisation; with `longest` given no
-        host value depends on device data and the whole call can be captured in a hipGraph); stack: episode_decode."""
+        host value depends on device data and the whole call can be captured in a hipGraph); stack, fuse_masks:
+        episode_decode."""
         enc_out, hidden, feat0 = self._encode_request(x, lengths, img_x, self.opt.decoder_max_len > 0, longest)
-        return self.episode_decode(x, img_x, enc_out, hidden, mask_dict, reinforce_sample, feat0, stack)
+        return self.episode_decode(x, img_x, enc_out, hidden, mask_dict, reinforce_sample, feat0, stack, fuse_masks)
 
-    def episode_decode(self, x, img_x, enc_out, hidden, mask_dict=None, reinforce_sample=1, feat0=None, stack=True):
+    def episode_decode(self, x, img_x, enc_out, hidden, mask_dict=None, reinforce_sample=1, feat0=None, stack=True, fuse_masks=False):
         """The free-running decode of episode_forward from an encoded request (enc_out (B,L,d), hidden = decoder initial
         state): everything after the request encoder (actor.py:213-284).  No host synchronisation when mask_dict is None,
         so a whole train step from here on can be captured in one hipGraph (graphs.GraphedEpisodeStep).
-        stack=False: pred_imgs is returned as the list of T images (no (B,T,3,H,W) copy; `state` is then None)."""
+        stack=False: pred_imgs is returned as the list of T images (no (B,T,3,H,W) copy; `state` is then None).
+        fuse_masks=True with a gier.MaskTable: no per-step fp32 mask exists -- every step's operator kernels read the uint8
+        planes themselves (functional.apply_planes; images and gradients bit-identical) and state['masks'] is None."""
+        fuse = bool(fuse_masks) and self._is_table(mask_dict)
         B = img_x.shape[0]
         dev = img_x.device
         hiddens = [tuple(h.detach() for h in hidden)] if stack else None
@@ -262,8 +281,9 @@ class Actor(nn.Module):
                 op_mask.scatter_(1, pred_op, 0.0)          # an operator is used at most once
             pred_mask = None
             if mask_dict is not None:                      # local edits (GIER): a MaskTable stays on the device; a list of
-                pred_mask = self.step_mask(img_x, mask_dict, pred_op)      # dicts costs one host sync per step, as the reference
-                pred_masks.append(pred_mask)
+                pred_mask = self.step_mask(img_x, mask_dict, pred_op, fuse)      # dicts costs one host sync per step, as the reference
+                if not fuse:
+                    pred_masks.append(pred_mask)
             img_x, par = self._execute(img_x, pred_op, context, pred_mask, exec_op)
             pred_imgs.append(img_x)
             pred_params.append(par)

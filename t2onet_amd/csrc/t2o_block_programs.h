@@ -90,6 +90,24 @@ T2O_HD void store_vec(float* p, const float (&r)[V]) {
 
 T2O_HD float sign_of(float d) { return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f); }
 
+// Mask fetch: WHERE a masked program gets its mask values from.  This one, the default of every program below, reads the
+// fp32 mask tensor of OpArgs; t2o_plane_programs.h has the one that reads a uint8 plane where it lies.  A fetch only
+// produces values -- blend, clamp and every gradient formula stay the program's -- so two fetches that return equal floats
+// give bit-identical results.
+//   group<V>(m, px, r)  V consecutive values of one mask plane from pixel px on (m: the plane pointer the program derived
+//                       from OpArgs::mask, meaningless to other fetches)
+//   at(a, b, c, px)     one value of sample b, channel c
+#if defined(__HIPCC__)
+#define T2O_HD_MEMBER __host__ __device__ __forceinline__
+#else
+#define T2O_HD_MEMBER inline            // (T2O_HD is `static inline` for g++: not for member functions)
+#endif
+struct MaskF32 {
+  template <int V>
+  T2O_HD_MEMBER void group(const float* m, unsigned px, float (&r)[V]) const { load_vec<V>(m + px, r); }
+  T2O_HD_MEMBER float at(const OpArgs& a, int b, int c, size_t px) const { return mask_at(a, b, c, px); }
+};
+
 // ===================================================================== curve lookup table
 // Curves use a per-sample table (in LDS on the device): knots k[c][8], running sums
 // P[c][j] = sum_{i<j} k_i/8 accumulated in the reference's order, sum[c], scale[c] and 1/sum[c].  For a
@@ -170,8 +188,8 @@ struct SampleView {
 
 // Forward: one thread, `iters` groups of V consecutive pixels of sample b.
 // Returns this thread's partial sum of |out - target| (0 when not L1).
-template <int V, bool MASKED, bool L1>
-T2O_HD float pointwise_fwd_thread(const OpArgs& a, int op, int b, int blk, int tid) {
+template <int V, bool MASKED, bool L1, class MF = MaskF32>
+T2O_HD float pointwise_fwd_thread(const OpArgs& a, int op, int b, int blk, int tid, const MF& mf = MF()) {
   const unsigned hw = (unsigned)a.H * (unsigned)a.W;
   const unsigned groups = hw / V;
   const size_t sb = (size_t)b * 3 * hw;
@@ -194,7 +212,7 @@ T2O_HD float pointwise_fwd_thread(const OpArgs& a, int op, int b, int blk, int t
     T2O_UNROLL
     for (int c = 0; c < 3; ++c) {
       load_vec<V>(s.x + c * hw + px, x[c]);
-      if (MASKED && (c == 0 || s.mstride)) load_vec<V>(s.m + c * s.mstride + px, mk[c]);
+      if (MASKED && (c == 0 || s.mstride)) mf.template group<V>(s.m + c * s.mstride, px, mk[c]);
     }
     T2O_UNROLL
     for (int i = 0; i < V; ++i) {
@@ -229,8 +247,9 @@ T2O_HD float pointwise_fwd_thread(const OpArgs& a, int op, int b, int blk, int t
 // Backward: recompute the forward (for the clamp test), apply the closed-form
 // derivative, write gimg, accumulate raw parameter-gradient sums into red[].
 // `tab`: this sample's curve lookup table (curve_table_build), used when op is a curve operator.
-template <int V, bool MASKED, bool L1>
-T2O_HD void pointwise_bwd_thread(const OpArgs& a, int op, int b, int blk, int tid, float (&red)[kRedSlots], const float* tab) {
+template <int V, bool MASKED, bool L1, class MF = MaskF32>
+T2O_HD void pointwise_bwd_thread(const OpArgs& a, int op, int b, int blk, int tid, float (&red)[kRedSlots], const float* tab,
+                                 const MF& mf = MF()) {
   const unsigned hw = (unsigned)a.H * (unsigned)a.W;
   const unsigned groups = hw / V;
   const size_t sb = (size_t)b * 3 * hw;
@@ -253,7 +272,7 @@ T2O_HD void pointwise_bwd_thread(const OpArgs& a, int op, int b, int blk, int ti
     for (int c = 0; c < 3; ++c) {
       load_vec<V>(s.x + c * hw + px, x[c]);
       load_vec<V>(s.g + c * hw + px, gg[c]);
-      if (MASKED && (c == 0 || s.mstride)) load_vec<V>(s.m + c * s.mstride + px, mk[c]);
+      if (MASKED && (c == 0 || s.mstride)) mf.template group<V>(s.m + c * s.mstride, px, mk[c]);
     }
     if (op == OP_TONE || op == OP_COLOR) {
       // channels are independent: run the thread's 3V pixel-channels strictly one after another
@@ -418,8 +437,8 @@ T2O_HD Sides quad_sides(const float* lds, int halo, int c, int r, int j0, const 
   return s;
 }
 
-template <int V>
-T2O_HD float sharp_fwd_phase_compute(const OpArgs& a, int b, int tile, int tid, const float* lds) {
+template <int V, class MF = MaskF32>
+T2O_HD float sharp_fwd_phase_compute(const OpArgs& a, int b, int tile, int tid, const float* lds, const MF& mf = MF()) {
   int y0, x0;
   tile_origin(a, tile, y0, x0);
   const int ty = tid / (kTileW / 4), tx = tid % (kTileW / 4);
@@ -440,7 +459,7 @@ T2O_HD float sharp_fwd_phase_compute(const OpArgs& a, int b, int tile, int tid, 
       const float left = i == 0 ? L : ce[i > 0 ? i - 1 : 0], right = i == 3 ? R : ce[i < 3 ? i + 1 : 3];
       const float d = sharp_delta(ce[i], up[i], left, right, dn[i]);
       float z = ce[i] + p * d;
-      if (a.mask_ch && live && gx0 + i < a.W) z = blend(z, ce[i], mask_at(a, b, c, (size_t)gy * a.W + gx0 + i));
+      if (a.mask_ch && live && gx0 + i < a.W) z = blend(z, ce[i], mf.at(a, b, c, (size_t)gy * a.W + gx0 + i));
       o[i] = clamp01(z);
     }
     if (!live) continue;

@@ -82,10 +82,14 @@ class Executor(nn.Module):
 
     def execute_per_sample(self, img, op_ids, mask, features=None, specified_param=None):
         """op_ids: (B,) integer tensor on the GPU of executor indices (-1 = identity).
-        Returns (out (B,3,H,W), param (B,24)) like the per-group loop + regroup of actor.py:244-259."""
+        Returns (out (B,3,H,W), param (B,24)) like the per-group loop + regroup of actor.py:244-259.
+        mask: None, a (B,1|3,H,W) tensor, or a functional.PlaneMask -- the uint8 planes of a gier.MaskTable read in place
+        (functional.apply_planes: the same bits as the tensor mask_select would make, without making it)."""
         assert (features is None) ^ (specified_param is None)
         op_ids = op_ids.to(torch.int32)
         param = self.predict_params(op_ids, features) if features is not None else specified_param
+        if isinstance(mask, T.PlaneMask):
+            return T.apply_planes(op_ids, mask.pred_op, img, param, mask.planes, mask.slot), param
         return T.apply_per_sample(op_ids, img, param, mask), param
 
     @staticmethod

@@ -3,6 +3,7 @@ straight to the C ABI; torch only owns the memory and the autograd graph.
 
 Every function requires CUDA(HIP) fp32 tensors and raises otherwise -- there is no CPU path.
 """
+import collections
 import ctypes
 
 import os
@@ -2194,6 +2195,74 @@ def mask_select(planes, slot, pred_op):
                                      _stream(planes.device))
     replay_status(rc, 't2o_mask_select')
     return out
+
+
+PlaneMask = collections.namedtuple('PlaneMask', 'planes slot pred_op')
+PlaneMask.__doc__ = """The mask of one masked step as the device holds it: planes (N,H,W) uint8 and slot (B,V) int32 of a gier.MaskTable,
+pred_op (B,) or (B,1) int64 the operator vocabulary id each sample chose.  Executor.execute_per_sample takes one as `mask`:
+apply_planes then reads the bytes where they lie instead of a (B,1,H,W) fp32 tensor from mask_select."""
+
+
+def _plane_args(planes, slot, pred_op, img):
+    """The argument checks of mask_select, plus the image's shape."""
+    if not (planes.is_cuda and planes.dtype == torch.uint8 and planes.dim() == 3 and planes.is_contiguous()):
+        raise RuntimeError('apply_planes: planes must be a contiguous (N,H,W) uint8 GPU tensor; there is no CPU implementation')
+    if not (slot.is_cuda and slot.dtype == torch.int32 and slot.dim() == 2 and slot.is_contiguous()):
+        raise RuntimeError('apply_planes: slot must be a contiguous (B,V) int32 GPU tensor')
+    pred_op = pred_op.detach().reshape(-1)
+    if not (pred_op.is_cuda and pred_op.dtype == torch.int64 and pred_op.is_contiguous() and pred_op.numel() == slot.shape[0]):
+        raise RuntimeError('apply_planes: pred_op must be a contiguous int64 GPU tensor of B elements')
+    if slot.shape[0] != img.shape[0] or tuple(planes.shape[1:]) != tuple(img.shape[2:]):
+        raise ValueError('apply_planes: planes %s / slot %s do not belong to images %s' % (tuple(planes.shape), tuple(slot.shape), tuple(img.shape)))
+    return pred_op
+
+
+class _ApplyPlanesFn(torch.autograd.Function):
+    """apply_per_sample under mask_select's mask without the fp32 mask (t2o_apply_planes_fwd / _bwd): saves img, param and
+    the ids; the backward reads the same bytes again."""
+
+    @staticmethod
+    def forward(ctx, img, param, planes, slot, pred_op, op_id):
+        _need_gpu(img, param)
+        if op_id.dtype != torch.int32 or not op_id.is_cuda:
+            raise RuntimeError('op_id must be an int32 GPU tensor')
+        img = _img(img)
+        param = param.contiguous()
+        op_id = op_id.contiguous()
+        pred_op = _plane_args(planes, slot, pred_op, img)
+        B, _, H, W = img.shape
+        if param.shape != (B, PARAM_PAD):
+            raise ValueError('param must be (B,24)')
+        N, V = planes.shape[0], slot.shape[1]
+        out = torch.empty_like(img)
+        rc = _lib.load().t2o_apply_planes_fwd(_ptr(op_id), _ptr(pred_op), _ptr(planes) if N else None, _ptr(slot), N, V, _ptr(img),
+                                              _ptr(param), PARAM_PAD, _ptr(out), B, H, W, _stream(img.device))
+        _lib.check(rc, 't2o_apply_planes_fwd')
+        ctx.save_for_backward(img, param, planes, slot, pred_op, op_id)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        img, param, planes, slot, pred_op, op_id = ctx.saved_tensors
+        B, _, H, W = img.shape
+        N, V = planes.shape[0], slot.shape[1]
+        gout = gout.contiguous()
+        gimg = torch.empty_like(img) if ctx.needs_input_grad[0] else None
+        gparam = torch.zeros_like(param)
+        ws = workspace(B, H, W, img.device)
+        rc = _lib.load().t2o_apply_planes_bwd(_ptr(op_id), _ptr(pred_op), _ptr(planes) if N else None, _ptr(slot), N, V, _ptr(img),
+                                              _ptr(param), PARAM_PAD, _ptr(gout), _ptr(gimg), _ptr(gparam), PARAM_PAD, _ptr(ws),
+                                              ws.numel(), B, H, W, _stream(img.device))
+        _lib.check(rc, 't2o_apply_planes_bwd')
+        return gimg, gparam, None, None, None, None
+
+
+def apply_planes(op_id, pred_op, img, param, planes, slot):
+    """apply_per_sample(op_id, img, param, mask_select(planes, slot, pred_op)) in one launch and bit for bit the same out,
+    image and parameter gradients: the kernels read the uint8 planes where they lie (no (B,1,H,W) fp32 mask is written,
+    read back or kept for the backward).  op_id (B,) int32 executor indices (-1 = identity), pred_op (B,) / (B,1) int64
+    operator vocabulary ids -- the column of `slot` --, planes (N,H,W) uint8, slot (B,V) int32; a count, not divided by 255."""
+    return _ApplyPlanesFn.apply(img, param, planes, slot, pred_op, op_id)
 
 
 # ---- mask feathering (t2o_feather.hip): the soft edge of a local edit, an exact integer Gaussian on uint8 planes ----

@@ -500,7 +500,8 @@ class GIERDatasetAct(GIERDataset):
 
 class _Tuples(Dataset):
     """A GIER dataset as the tuples the train / evaluation loops take: (img_x, img_y, x, req) or, with actions,
-    (img_x, img_ys, x, ops, params, req).  with_masks: a trailing dict, the item's 'mask_rle' (batch size 1 loops)."""
+    (img_x, img_ys, x, ops, params, req).  with_masks: a trailing dict, the item's 'mask_rle' (batch size 1 loops; batches
+    through collate_masks)."""
 
     def __init__(self, base, with_masks=False):
         self.base, self.with_masks = base, with_masks
@@ -511,7 +512,16 @@ class _Tuples(Dataset):
     def __getitem__(self, i):
         d = self.base[i]
         if 'operations' in d:
-            return d['input'], d['output'], d['request_idx'], torch.from_numpy(d['operations']), torch.from_numpy(d['parameters']), d['request']
+            t = d['input'], d['output'], d['request_idx'], torch.from_numpy(d['operations']), torch.from_numpy(d['parameters']), d['request']
+            return t + (d.get('mask_rle', {}),) if self.with_masks else t
         if self.with_masks:
             return d['input'], d['output'], d['request_idx'], d['request'], d.get('mask_rle', {})
         return d['input'], d['output'], d['request_idx'], d['request']
+
+
+def collate_masks(batch):
+    """DataLoader collate for _Tuples(..., with_masks=True): the tensors stacked as the default collate stacks them, each
+    item's 'mask_rle' dict kept as it is in a list beside them -- what MaskTable.from_rle takes (the operators differ from
+    item to item, so the dicts cannot be merged key by key)."""
+    from torch.utils.data import default_collate
+    return tuple(default_collate([item[:-1] for item in batch])) + ([item[-1] for item in batch],)

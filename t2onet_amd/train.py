@@ -260,6 +260,9 @@ class Trainer:
         self.graph_step = graph_step
         self._step_graphs = {}
         self.max_step_graphs = 4                            # distinct (shape, request length) keys kept; others run eagerly
+        # local edits (a gier.MaskTable handed to the steps): True = the operator kernels read the uint8 planes in place
+        # (functional.apply_planes), False = one mask_select launch + one fp32 mask per step.  Same bits either way.
+        self.fuse_masks = True
         # transformed convolution weights of the encoder trunk live for a whole optimiser step (encoder.TrunkPlan)
         enc = getattr(model, 'vis_encoder', None)
         self._trunk = enc.trunk_plan() if (enc is not None and self.grads.flat.is_cuda and hasattr(enc, 'trunk_plan')) else None
@@ -414,14 +417,29 @@ class Trainer:
         self._update()
         return loss
 
-    def supervised_step(self, x, y, img_x, img_y, gt_params, lengths=None):
-        """train_seq2seqL1.py:51-65: NLL (mean, no ignore_index) + MSE(sum)/count_nonzero."""
+    def _masked_eager(self, masks):
+        """A step with masks runs without the captured graphs: the number of planes changes from batch to batch, and a
+        capture fixes every shape.  The per-pass encoder graphs are set aside for the step (restored by the returned
+        callable); the whole-step graph is simply not taken."""
+        graphed = self.model.__dict__.pop('_graphed_encoders', None) if masks is not None else None
+
+        def restore():
+            if graphed is not None:
+                self.model.__dict__['_graphed_encoders'] = graphed
+        return restore
+
+    def supervised_step(self, x, y, img_x, img_y, gt_params, lengths=None, masks=None):
+        """train_seq2seqL1.py:51-65: NLL (mean, no ignore_index) + MSE(sum)/count_nonzero.
+        masks: a gier.MaskTable for local edits -- step i runs under the plane of the planned operator y[:, i]."""
         step = int((y != self.opt.null_id).sum(1).max())
-        self._maybe_graph(img_x)
+        if masks is None:
+            self._maybe_graph(img_x)
+        restore = self._masked_eager(masks)
         try:
             self._tape(img_x.shape[0])
             self._arena(img_x, step - 1)
-            _, pred_params, logp = self.model.supervised_forward(x, y, img_x, img_y, gt_params, None, lengths)
+            _, pred_params, logp = self.model.supervised_forward(x, y, img_x, img_y, gt_params, masks, lengths,
+                                                                 fuse_masks=self.fuse_masks)
             target = y[:, 1:step].contiguous().view(-1)
             op_loss = F.nll_loss(logp.reshape(-1, logp.shape[-1]), target)
             gt = gt_params[:, :step - 2]
@@ -429,29 +447,37 @@ class Trainer:
             self._finish(op_loss + param_loss)
         finally:
             self._release()
+            restore()
         return op_loss.detach(), param_loss.detach()
 
-    def episode_step(self, x, img_x, target, reinforce_sample=1, lengths=None):
-        """train_seq2seqL1.py:74-88: free-running episode, L1 between the END image and the target."""
-        if self.graph_step:
+    def episode_step(self, x, img_x, target, reinforce_sample=1, lengths=None, masks=None):
+        """train_seq2seqL1.py:74-88: free-running episode, L1 between the END image and the target.
+        masks: a gier.MaskTable for local edits -- every step runs under the plane of the operator it chose.  Such a step
+        bypasses graph_step / graph_encoder (see _masked_eager)."""
+        if self.graph_step and masks is None:
             loss = self._graphed_episode_step(x, img_x, target, reinforce_sample, lengths)
             if loss is not None:
                 return loss
-        self._maybe_graph(img_x)
+        if masks is None:
+            self._maybe_graph(img_x)
+        restore = self._masked_eager(masks)
         try:
             self._tape(img_x.shape[0])
             self._arena(img_x, self.opt.decoder_max_len)
-            _, pred_imgs, pred_ops, _ = self.model.episode_forward(x, img_x, None, reinforce_sample, lengths, stack=False)
+            _, pred_imgs, pred_ops, _ = self.model.episode_forward(x, img_x, masks, reinforce_sample, lengths, stack=False,
+                                                                   fuse_masks=self.fuse_masks)
             loss = end_l1_loss(pred_imgs, pred_ops, self.opt.end_id, target)
             self._finish(loss)
         finally:
             self._release()
+            restore()
         return loss.detach()
 
-    def step(self, batch):
-        """batch = (img_x, img_y (B,6,3,H,W), x, y, gt_params) as the reference's loader yields."""
+    def step(self, batch, masks=None):
+        """batch = (img_x, img_y (B,6,3,H,W), x, y, gt_params) as the reference's loader yields; masks: a gier.MaskTable
+        of the batch (local edits) or None."""
         self.itr += 1
         img_x, img_y, x, y, gt_params = batch
         if self.itr % 2 == 1:
-            return self.supervised_step(x, y, img_x, img_y, gt_params)
-        return self.episode_step(x, img_x, img_y[:, -1])
+            return self.supervised_step(x, y, img_x, img_y, gt_params, masks=masks)
+        return self.episode_step(x, img_x, img_y[:, -1], masks=masks)

@@ -12,7 +12,9 @@ word vectors (fix_input_embedding) -- synthetic runs train the whole table inste
 Real data: --img_dir/--anno_dir/--act_dir with the reference's FiveK layout (datasets/FiveKdataset.py), or
 --dataset GIER --data_dir data/GIER --act_dir output/GIER_actions_set_1 --data_mode valid [--session 3] with the reference's
 GIER layout (train_GIER_seq2seqL1.py: gier.GIERDatasetAct for training, gier.GIERDataset('val') for validation, GIER's
-vocabularies, global edits only).
+vocabularies; global edits unless --load_mask: the annotated regions' run lengths ride with each batch, one
+gier.MaskTable.from_rle per batch (one upload, one launch) and both train steps run their local operators under the masks,
+the operator kernels reading the uint8 planes in place; score such a checkpoint with gier_cli --load_mask).
 """
 import argparse
 import json
@@ -92,7 +94,11 @@ def parse_args(argv=None):
                     help='real data: the loaders only decode; resize + layout run on the GPU, one launch per batch')
     ap.add_argument('--device_eval', action='store_true',
                     help='validation through evaluate.test_on_device: one fused metrics launch per image, one host read per pass')
+    ap.add_argument('--load_mask', action='store_true',
+                    help='GIER: train local edits under their annotated masks (device-resident uint8 planes, read in place)')
     args = ap.parse_args(argv)
+    if args.load_mask and args.dataset != 'GIER':
+        ap.error('--load_mask needs --dataset GIER: only GIER annotates regions')
     if args.session is None:
         args.session = 3 if args.dataset == 'GIER' else 1
     if args.dataset == 'GIER' and (args.synthetic or args.device_resize):
@@ -130,17 +136,17 @@ def main(argv=None):
     raw = args.device_resize and not args.synthetic
     if gier_run:
         # train_GIER_seq2seqL1.py:157-164: GIERDatasetAct for training, GIERDataset('val') for validation, is_load_mask = False
-        # (global edits only); the vocabularies are GIER's (options.dataset -> actor._vocab_sizes)
-        from .gier import GIERDataset, GIERDatasetAct, _Tuples
-        dataset = _Tuples(GIERDatasetAct(args.data_dir, args.vocab_dir, args.act_dir, 'train', args.data_mode, False, args.session,
-                                         args.img_size))
+        # (global edits only) unless --load_mask; the vocabularies are GIER's (options.dataset -> actor._vocab_sizes)
+        from .gier import GIERDataset, GIERDatasetAct, MaskTable, _Tuples, collate_masks
+        dataset = _Tuples(GIERDatasetAct(args.data_dir, args.vocab_dir, args.act_dir, 'train', args.data_mode,
+                                         'rle' if args.load_mask else False, args.session, args.img_size), with_masks=args.load_mask)
     else:
         dataset = SyntheticFiveK(n=args.batch_size * 64, size=args.img_size) if args.synthetic else \
             FiveKAct(args.img_dir, args.anno_dir, args.act_dir, 'train', 1, args.img_size, raw=raw)
     sampler = DistributedSampler(dataset, world, rank, shuffle=True) if world > 1 else None
     raw_kw = dict(collate_fn=collate_raw, pin_memory=True) if raw else {}
     loader = DataLoader(dataset, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler,
-                        num_workers=args.num_workers, drop_last=True, **raw_kw)
+                        num_workers=args.num_workers, drop_last=True, **(dict(collate_fn=collate_masks) if args.load_mask else raw_kw))
     if gier_run:
         val_loader = DataLoader(_Tuples(GIERDataset(args.data_dir, args.vocab_dir, 'val', args.data_mode, False, args.session)),
                                 batch_size=1, shuffle=False, num_workers=1)
@@ -167,17 +173,21 @@ def main(argv=None):
             tik = time.time()
             if raw:                                                  # decoded bytes: one upload, one resize launch
                 batch = device_batch(batch, args.img_size, device, images_only=True)
+            masks = None
+            if args.load_mask:                                       # the batch's union planes: one upload, one launch
+                batch, rles = batch[:-1], batch[-1]
+                masks = MaskTable.from_rle(rles, (args.img_size, args.img_size), model.decoder.output_size, device)
             img_x, img_y, x, y, gt_params, _ = batch
             lengths = (x != opt.null_id).sum(1)
             x, y, img_x, img_y, gt_params = (t.to(device, non_blocking=True) for t in (x, y, img_x, img_y, gt_params))
             if itr % 2 == 1:
-                op_loss, param_loss = trainer.supervised_step(x, y, img_x, img_y, gt_params, lengths)
+                op_loss, param_loss = trainer.supervised_step(x, y, img_x, img_y, gt_params, lengths, masks=masks)
                 k = 1.0 / (itr // 2 + 1)
                 if itr % args.print_every in (0, 1):                 # .item() only when printing
                     avg['op'], avg['param'] = op_loss.item(), param_loss.item()
                 avg['fs_t'] += (time.time() - tik - avg['fs_t']) * k
             else:
-                l1 = trainer.episode_step(x, img_x, img_y[:, -1], lengths=lengths)
+                l1 = trainer.episode_step(x, img_x, img_y[:, -1], lengths=lengths, masks=masks)
                 k = 1.0 / (itr // 2)
                 if itr % args.print_every == 0:
                     avg['l1'] = l1.item()
