@@ -930,8 +930,8 @@ T2O_HD float chain_fwd_thread_static(const ChainArgs& a, int b, int blk, int tid
   return l1;
 }
 
-template <bool L1, class SEQ, bool SV_LDS, class ACC, bool VAL = L1>
-T2O_HD float chain_bwd_thread_static(const ChainArgs& a, int b, int blk, int tid, const float* tab, float* svl, ACC& acc) {
+template <bool L1, class SEQ, class ACC, bool VAL = L1>
+T2O_HD float chain_bwd_thread_static(const ChainArgs& a, int b, int blk, int tid, const float* tab, ACC& acc) {
   constexpr int K = SEQ::K;
   float l1 = 0.0f;                                   // (L1 forms: sum |chain(img) - target| of the live pixels, see chain_bwd_thread)
   const unsigned hw = (unsigned)a.H * (unsigned)a.W;
@@ -956,7 +956,7 @@ T2O_HD float chain_bwd_thread_static(const ChainArgs& a, int b, int blk, int tid
     const unsigned g = ((unsigned)blk * a.iters + it) * kThreads + tid;
     const bool live = g < hw;                        // dead threads carry zeros into the reductions
     const unsigned px = live ? g : 0;
-    float x[3], gg[3], sv[SV_LDS ? 1 : K][3];        // SV_LDS: operator inputs saved in the LDS area instead (fewer registers)
+    float x[3], gg[3], sv[K][3];                     // sv: the operators' inputs, kept in registers for the way back
     bool pass[K][3];                                 // clamp passed? -- lane masks in scalar registers, no vector register
     T2O_UNROLL
     for (int c = 0; c < 3; ++c) { x[c] = xn[c]; gg[c] = gn[c]; }
@@ -970,9 +970,7 @@ T2O_HD float chain_bwd_thread_static(const ChainArgs& a, int b, int blk, int tid
     for (int k = 0; k < K; ++k) {
       Rgb xi = {{x[0], x[1], x[2]}};
       T2O_UNROLL
-      for (int c = 0; c < 3; ++c) {
-        if (SV_LDS) svl[(k * 3 + c) * kThreads + tid] = xi.c[c]; else sv[k][c] = xi.c[c];
-      }
+      for (int c = 0; c < 3; ++c) sv[k][c] = xi.c[c];
       const Rgb r = chain_op_fwd(SEQ::ops[k], xi, tab + k * kTabStride, k > 0);   // k > 0: xi = clamp01(...)
       T2O_UNROLL
       for (int c = 0; c < 3; ++c) {
@@ -1003,7 +1001,7 @@ T2O_HD float chain_bwd_thread_static(const ChainArgs& a, int b, int blk, int tid
       Rgb xi, gi;
       T2O_UNROLL
       for (int c = 0; c < 3; ++c) {
-        xi.c[c] = SV_LDS ? svl[(k * 3 + c) * kThreads + tid] : sv[k][c];
+        xi.c[c] = sv[k][c];
         gi.c[c] = pass[k][c] ? gg[c] : 0.0f;
       }
       Rgb gx;
@@ -1029,6 +1027,12 @@ T2O_HD float chain_bwd_thread_static(const ChainArgs& a, int b, int blk, int tid
     else if (op != OP_WHITE) { float (&r)[1] = reinterpret_cast<float (&)[1]>(red[k]); acc.template add_n<1>(a.bin_off[k], r); }
   }
   return l1;
+}
+// The call form of earlier revisions, <L1, SEQ, false> with a save-area pointer before `acc` (a variant that kept the
+// operator inputs in LDS took both; it is gone): forwards, so that a harness written against that form still compiles.
+template <bool L1, class SEQ, bool, class ACC, bool VAL = L1>
+T2O_HD float chain_bwd_thread_static(const ChainArgs& a, int b, int blk, int tid, const float* tab, float*, ACC& acc) {
+  return chain_bwd_thread_static<L1, SEQ, ACC, VAL>(a, b, blk, tid, tab, acc);
 }
 
 // ===================================================================== SSIM (evaluation metric)

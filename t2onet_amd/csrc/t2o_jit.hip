@@ -93,7 +93,7 @@ std::string chain_source(const int* ops, int K) {
   for (int k = 0; k < K; ++k) seq += (k ? ", " : "") + std::to_string(ops[k]);
   std::string s = "#include \"t2o_chain_kernels.h\"\nusing SEQ = t2o::StaticChain<" + seq + ">;\n";
   const char* fmt_fwd = "extern \"C\" __global__ __launch_bounds__(256) void %s(t2o::ChainArgs a) { t2o::chain_fwd_static_body<%d, %s, SEQ>(a); }\n";
-  const char* fmt_bwd = "extern \"C\" __global__ __launch_bounds__(256) void %s(t2o::ChainArgs a) { t2o::chain_bwd_static_body<%s, SEQ, false>(a); }\n";
+  const char* fmt_bwd = "extern \"C\" __global__ __launch_bounds__(256) void %s(t2o::ChainArgs a) { t2o::chain_bwd_static_body<%s, SEQ>(a); }\n";
   char line[512];
   for (int v = 1; v <= 2; ++v)
     for (int l1 = 0; l1 < 2; ++l1) {

@@ -166,8 +166,8 @@ __global__ __launch_bounds__(kThreads) void k_chain_bwd(ChainArgs a) {
 
 // the backward for an operator list fixed at compile time: body in t2o_chain_kernels.h (shared with the hipRTC path,
 // t2o_fused_sequence_prepare).  One instantiation per entry of the dispatch in fused_chain_launch_bwd.
-template <bool L1, class SEQ, bool SV_LDS, int MINW, bool VAL = false>
-__global__ __launch_bounds__(kThreads, MINW) void k_chain_bwd_static(ChainArgs a) { chain_bwd_static_body<L1, SEQ, SV_LDS, VAL>(a); }
+template <bool L1, class SEQ, bool VAL = false>
+__global__ __launch_bounds__(kThreads, 1) void k_chain_bwd_static(ChainArgs a) { chain_bwd_static_body<L1, SEQ, VAL>(a); }
 
 // one workgroup per sample: per-block sums -> raw sums -> parameter gradients of every chain operator.
 // 8 threads per slot walk the block rows (stride 8), then a fixed-order LDS combine.
@@ -787,11 +787,6 @@ __global__ __launch_bounds__(kThreads) void k_attn_bwd(const float* q, const flo
 }
 
 // ------------------------------------------------------------------ host-side launch logic
-int env_int(const char* name, int dflt) {
-  const char* s = getenv(name);
-  return s ? atoi(s) : dflt;
-}
-
 Geometry launch_geometry(int B, int H, int W) {
   constexpr int forced = 0;                            // (pixel groups per thread: derived from the image size)
   return t2o::geometry(B, H, W, forced);
@@ -1232,13 +1227,13 @@ static bool chain_is(const ChainArgs& a) {
     if (a.ops[k] != SEQ::ops[k]) return false;
   return true;
 }
-template <class SEQ, bool SV_LDS, int MINW>
+template <class SEQ>
 static void launch_static_bwd(ChainArgs& a, bool l1, hipStream_t st) {
   const unsigned grid = (unsigned)a.B * a.nblk;
-  const size_t lds = sizeof(float) * ((size_t)a.bin_off[kMaxChain] * kAccStride + (SV_LDS ? chain_save_floats<1>(SEQ::K) : 0));
-  if (l1 && a.loss_partials) k_chain_bwd_static<true, SEQ, SV_LDS, MINW, true><<<grid, kThreads, lds, st>>>(a);      // value-and-gradient
-  else if (l1) k_chain_bwd_static<true, SEQ, SV_LDS, MINW><<<grid, kThreads, lds, st>>>(a);
-  else k_chain_bwd_static<false, SEQ, SV_LDS, MINW><<<grid, kThreads, lds, st>>>(a);
+  const size_t lds = sizeof(float) * (size_t)a.bin_off[kMaxChain] * kAccStride;
+  if (l1 && a.loss_partials) k_chain_bwd_static<true, SEQ, true><<<grid, kThreads, lds, st>>>(a);      // value-and-gradient
+  else if (l1) k_chain_bwd_static<true, SEQ><<<grid, kThreads, lds, st>>>(a);
+  else k_chain_bwd_static<false, SEQ><<<grid, kThreads, lds, st>>>(a);
 }
 template <class SEQ>
 static void launch_static_fwd(ChainArgs& a, int vec, bool l1, hipStream_t st) {
@@ -1247,34 +1242,20 @@ static void launch_static_fwd(ChainArgs& a, int vec, bool l1, hipStream_t st) {
   else          { if (l1) k_chain_fwd_static<1, true, SEQ><<<grid, kThreads, 0, st>>>(a); else k_chain_fwd_static<1, false, SEQ><<<grid, kThreads, 0, st>>>(a); }
 }
 
-template <class SEQ>
-static void launch_static_bwd_variant(ChainArgs& a, int variant, bool l1, hipStream_t st) {
-  switch (variant) {
-    case 2: launch_static_bwd<SEQ, true, 1>(a, l1, st); break;       // operator inputs saved in LDS: no faster (106.9 vs 104.2 us)
-    default: launch_static_bwd<SEQ, false, 1>(a, l1, st); break;
-  }
-}
-
 extern "C" {
 
-static int chain_static_variant() {
-  static const int v = env_int("T2O_CHAIN_STATIC", 1);                   // 0: the run-time loop kernel for every list (A/B runs)
-  return v;
-}
 static bool chain_has_aot(const ChainArgs& a) { return chain_is<SeqCfg2>(a) || chain_is<SeqCfg5>(a); }
 static bool chain_has_static_bwd(const ChainArgs& a, int vec) {
-  if (vec != 1 || !chain_static_variant()) return false;
+  if (vec != 1) return false;
   t2o::JitChain j;
   return chain_has_aot(a) || t2o::jit_lookup(a.ops, a.K, &j);
 }
 
 static int fused_chain_launch_fwd(ChainArgs& a, int vec, bool l1, hipStream_t st) {
-  if (chain_static_variant()) {
-    if (chain_is<SeqCfg2>(a)) { launch_static_fwd<SeqCfg2>(a, vec, l1, st); return 0; }
-    if (chain_is<SeqCfg5>(a)) { launch_static_fwd<SeqCfg5>(a, vec, l1, st); return 0; }
-    t2o::JitChain j;                       // an operator list specialised at run time (t2o_fused_sequence_prepare)
-    if (t2o::jit_lookup(a.ops, a.K, &j)) return t2o::jit_launch(j.fwd[vec == 2 ? 1 : 0][l1 ? 1 : 0], a, (unsigned)a.B * a.nblk, 0, st);
-  }
+  if (chain_is<SeqCfg2>(a)) { launch_static_fwd<SeqCfg2>(a, vec, l1, st); return 0; }
+  if (chain_is<SeqCfg5>(a)) { launch_static_fwd<SeqCfg5>(a, vec, l1, st); return 0; }
+  t2o::JitChain j;                         // an operator list specialised at run time (t2o_fused_sequence_prepare)
+  if (t2o::jit_lookup(a.ops, a.K, &j)) return t2o::jit_launch(j.fwd[vec == 2 ? 1 : 0][l1 ? 1 : 0], a, (unsigned)a.B * a.nblk, 0, st);
   const unsigned grid = (unsigned)a.B * a.nblk;
   if (vec == 2) { if (l1) k_chain_fwd<2, true><<<grid, kThreads, 0, st>>>(a); else k_chain_fwd<2, false><<<grid, kThreads, 0, st>>>(a); }
   else          { if (l1) k_chain_fwd<1, true><<<grid, kThreads, 0, st>>>(a); else k_chain_fwd<1, false><<<grid, kThreads, 0, st>>>(a); }
@@ -1282,10 +1263,9 @@ static int fused_chain_launch_fwd(ChainArgs& a, int vec, bool l1, hipStream_t st
 }
 
 static int fused_chain_launch_bwd(ChainArgs& a, int vec, bool l1, hipStream_t st) {
-  const int use_static = chain_static_variant();
-  if (vec == 1 && use_static) {
-    if (chain_is<SeqCfg2>(a)) { launch_static_bwd_variant<SeqCfg2>(a, use_static, l1, st); return 0; }
-    if (chain_is<SeqCfg5>(a)) { launch_static_bwd_variant<SeqCfg5>(a, use_static, l1, st); return 0; }
+  if (vec == 1) {
+    if (chain_is<SeqCfg2>(a)) { launch_static_bwd<SeqCfg2>(a, l1, st); return 0; }
+    if (chain_is<SeqCfg5>(a)) { launch_static_bwd<SeqCfg5>(a, l1, st); return 0; }
     t2o::JitChain j;
     if (t2o::jit_lookup(a.ops, a.K, &j))
       return t2o::jit_launch(j.bwd[l1 ? 1 : 0], a, (unsigned)a.B * a.nblk, sizeof(float) * (size_t)a.bin_off[kMaxChain] * kAccStride, st);

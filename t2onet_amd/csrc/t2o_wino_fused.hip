@@ -2,8 +2,8 @@
 // 64- and 128-channel stages (models/actor_resnet.py:24-44 BasicBlock; 64 x 64 and 32 x 32 maps at bs = 64, 256 x 256 input).
 //
 //   The separate-pass pipeline of t2o_winograd.hip (input transform -> 16 GEMMs -> output transform) moves V and M, 4 x the
-//   activation each, through HBM: it wins at 256 / 512 channels (small maps) and loses badly at 64 / 128 (T2O_WINOGRAD_MIN_C
-//   = 128 measured +2 ms per step).  Here ONE launch does all of it per block of 8 x 8 tiles (16 x 16 output pixels of one
+//   activation each, through HBM: it wins at 256 / 512 channels (small maps) and loses badly at 64 / 128 (a threshold
+//   of 128 channels measured +2 ms per step).  Here ONE launch does all of it per block of 8 x 8 tiles (16 x 16 output pixels of one
 //   image) x 64 output channels:
 //     * the 18 x 18 input patch of the block arrives by LDS-DMA in chunks of 8 input channels (32 bytes per pixel);
 //     * the workgroup transforms a chunk to V[xi][tile][8] in LDS (B^T d B: 32 add/sub per (tile, channel));

@@ -19,25 +19,24 @@ autograd node with an explicit forward / backward schedule over the C ABI -- wha
 Arithmetic is that of the per-layer path (same kernels, same order inside every sum); tests/test_gpu_encoder.py holds
 both against fp64 autograd of the oracle's ResNet.
 """
-import os
-
 import torch
 
 from . import _lib
 from .functional import (_need_gpu, _persistent_grad, _ptr, _stream, _conv_workspace, _zero_block, wino_conv_nhwc, wino_fused_conv_nhwc, wino_wgrad_nhwc, wino_input,
                          wino_backward_nhwc, wino_dw_from, wino_fused_wgrad_nhwc)
 
-# Winograd F(2x2,3x3) for the stride-1 layers with >= 256 channels (t2o_winograd.hip); T2O_WINOGRAD=0: the direct kernels everywhere
-_WINOGRAD = os.environ.get('T2O_WINOGRAD', '1') != '0'
-_WINO_MIN_C = int(os.environ.get('T2O_WINOGRAD_MIN_C', '256'))
-_DUAL_BN = True      # a shortcut block's two batch norms in one pass each way (t2o_bn_dual_*); module switch for the tests
+# Module switches, read at call time: the tests patch them to hold one path against the other.  Nothing outside sets them.
+# Winograd F(2x2,3x3) for the stride-1 layers with >= _WINO_MIN_C channels (t2o_winograd.hip); False: the direct kernels everywhere
+_WINOGRAD = True
+_WINO_MIN_C = 256
+_DUAL_BN = True      # a shortcut block's two batch norms in one pass each way (t2o_bn_dual_*)
 # Winograd F(2x2,3x3) with V and M kept on chip for the stride-1 layers of the 64- / 128-channel stages (t2o_wino_fused.hip);
-# T2O_WINOGRAD_FUSED=0: the direct kernels there (A/B)
-_WINO_FUSED = os.environ.get('T2O_WINOGRAD_FUSED', '1') != '0'
-_BN_SUMS_EPILOGUE = True     # bn1's backward sums from the epilogue of conv2's data gradient (direct kernels); switch for the tests
+# False: the direct kernels there
+_WINO_FUSED = True
+_BN_SUMS_EPILOGUE = True     # bn1's backward sums from the epilogue of conv2's data gradient (direct kernels)
 # the weight gradient of the on-chip Winograd layers in the Winograd domain too, both transforms on chip (t2o_wino_wgrad.hip);
-# T2O_WINOGRAD_WGRAD=0: the direct weight-gradient kernel there (A/B)
-_WINO_WGRAD = os.environ.get('T2O_WINOGRAD_WGRAD', '1') != '0'
+# False: the direct weight-gradient kernel there
+_WINO_WGRAD = True
 
 
 def _fast_direct(stride, Hi, Wi, Wo):

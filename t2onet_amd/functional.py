@@ -6,8 +6,6 @@ Every function requires CUDA(HIP) fp32 tensors and raises otherwise -- there is 
 import collections
 import ctypes
 
-import os
-
 import numpy as np
 import torch
 
@@ -58,18 +56,20 @@ def _mask(mask, img):
 _ws_need = {}
 
 
-def _scratch(need, device):
+def _scratch(need, device, cache=None, floor=1 << 20):
     """Per-(device, stream) scratch of at least `need` bytes, grown on demand; kernels on one stream run in order, so one
-    buffer per stream is enough."""
+    buffer per stream is enough.  cache / floor: a caller that keeps buffers of its own (_feather_workspace)."""
+    if cache is None:
+        cache = _workspaces
     if torch.cuda.is_current_stream_capturing():
         # inside a hipGraph capture the buffer's address is baked into the graph: a private allocation from the graph's
         # pool (a cached buffer could be replaced -- freed -- by a later, larger request on the same stream)
-        return torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=device)
+        return torch.empty(max(need, floor), dtype=torch.uint8, device=device)
     key = (device.index, _stream(device))
-    ws = _workspaces.get(key)
+    ws = cache.get(key)
     if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=device)
-        _workspaces[key] = ws
+        ws = torch.empty(max(need, floor), dtype=torch.uint8, device=device)
+        cache[key] = ws
     return ws
 
 
@@ -472,20 +472,7 @@ def param_heads(features, op_ids, heads, consts, into_grad=False):
 def conv3x3_wgrad(x, dy):
     """Weight gradient of a 3x3 stride-1 padding-1 convolution on the fp32 matrix cores (t2o_conv3x3_wgrad_nhwc).
     x (N,Ci,H,W), dy (N,Co,H,W), both channels-last; returns dw (Co,Ci,3,3) channels-last."""
-    _need_gpu(x, dy)
-    N, Ci, H, W = x.shape
-    Co = dy.shape[1]
-    x = x.contiguous(memory_format=torch.channels_last)
-    dy = dy.contiguous(memory_format=torch.channels_last)
-    lib = _lib.load()
-    need = lib.t2o_conv3x3_wgrad_workspace_bytes(N, H, W, Ci, Co)
-    if need == 0:
-        raise RuntimeError('conv3x3_wgrad: unsupported shape (channels must be multiples of 64, the width a multiple of 4)')
-    ws = _conv_workspace(x.device, need)
-    dw = torch.empty((Co, Ci, 3, 3), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    rc = lib.t2o_conv3x3_wgrad_nhwc(_ptr(x), _ptr(dy), _ptr(dw), _ptr(ws), ws.numel(), N, H, W, Ci, Co, _stream(x.device))
-    _lib.check(rc, 't2o_conv3x3_wgrad_nhwc')
-    return dw
+    return _conv_wgrad('conv3x3_wgrad', x, dy, 1, 'channels must be multiples of 64, the width a multiple of 4')
 
 
 _conv_zeros = {}
@@ -512,97 +499,100 @@ def _zero_block(device):
     return _conv_zeros[idx]
 
 
-def conv3x3_forward(x, weight, want_stats=False):
-    """conv2d(x, weight, None, 1, 1) on the fp32 matrix cores (t2o_conv3x3_fwd_nhwc).  x (N,Ci,H,W) and weight
-    (Co,Ci,3,3) channels-last; returns y (N,Co,H,W) channels-last.  want_stats: returns (y, stats) with stats
-    (rows, 2, Co) = per pixel tile the channels' sums and sums of squares of y (t2o_conv3x3_fwd_stats_nhwc), the
-    input of batch_norm_relu(..., partial=stats)."""
+def _nhwc_empty(N, C, H, W, device):
+    return torch.empty((N, C, H, W), dtype=torch.float32, device=device, memory_format=torch.channels_last)
+
+
+def _conv_fwd(who, x, weight, stride, want_stats, hint):
+    """The body of conv3x3_forward (stride 1) and conv3x3s2_forward (stride 2)."""
     _need_gpu(x, weight)
-    N, Ci, H, W = x.shape
+    N, Ci, Hi, Wi = x.shape
     Co = weight.shape[0]
+    if stride == 2 and (Hi % 2 or Wi % 2):
+        raise ValueError('%s: the image size must be even' % who)
+    Ho, Wo = Hi // stride, Wi // stride
     x = x.contiguous(memory_format=torch.channels_last)
     weight = weight.contiguous(memory_format=torch.channels_last)
     lib = _lib.load()
-    need = lib.t2o_conv3x3_fwd_workspace_bytes(N, H, W, Ci, Co)
+    need = (lib.t2o_conv3x3_fwd_workspace_bytes if stride == 1 else lib.t2o_conv3x3s2_fwd_workspace_bytes)(N, Ho, Wo, Ci, Co)
     if need == 0:
-        raise RuntimeError('conv3x3_forward: unsupported shape (Ci % 32, Co % 64, W % 8 must be 0)')
+        raise RuntimeError('%s: unsupported shape (%s)' % (who, hint))
     ws = _conv_workspace(x.device, need)
-    y = torch.empty((N, Co, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    y = _nhwc_empty(N, Co, Ho, Wo, x.device)
     if want_stats:
-        stats = torch.empty((lib.t2o_conv3x3_fwd_stats_rows(N, H, W, Co, 1), 2, Co), dtype=torch.float32, device=x.device)
-        rc = lib.t2o_conv3x3_fwd_stats_nhwc(_ptr(x), _ptr(weight), _ptr(y), _ptr(stats), _ptr(ws), ws.numel(), N, H, W, Ci, Co, 1,
+        stats = torch.empty((lib.t2o_conv3x3_fwd_stats_rows(N, Ho, Wo, Co, stride), 2, Co), dtype=torch.float32, device=x.device)
+        rc = lib.t2o_conv3x3_fwd_stats_nhwc(_ptr(x), _ptr(weight), _ptr(y), _ptr(stats), _ptr(ws), ws.numel(), N, Ho, Wo, Ci, Co, stride,
                                             _stream(x.device))
         _lib.check(rc, 't2o_conv3x3_fwd_stats_nhwc')
         return y, stats
-    rc = lib.t2o_conv3x3_fwd_nhwc(_ptr(x), _ptr(weight), _ptr(y), _ptr(ws), ws.numel(), N, H, W, Ci, Co, _stream(x.device))
-    _lib.check(rc, 't2o_conv3x3_fwd_nhwc')
+    name = 't2o_conv3x3_fwd_nhwc' if stride == 1 else 't2o_conv3x3s2_fwd_nhwc'    # (the _stats entry refuses a null `stats`)
+    _lib.check(getattr(lib, name)(_ptr(x), _ptr(weight), _ptr(y), _ptr(ws), ws.numel(), N, Ho, Wo, Ci, Co, _stream(x.device)), name)
     return y
 
 
-def conv3x3_dgrad(dy, weight):
-    """Data gradient of conv2d(x, weight, None, 1, 1) (t2o_conv3x3_dgrad_nhwc).  dy (N,Co,H,W) and weight (Co,Ci,3,3)
-    channels-last; returns dx (N,Ci,H,W) channels-last."""
-    _need_gpu(dy, weight)
-    N, Co, H, W = dy.shape
-    Ci = weight.shape[1]
-    dy = dy.contiguous(memory_format=torch.channels_last)
-    weight = weight.contiguous(memory_format=torch.channels_last)
-    lib = _lib.load()
-    need = lib.t2o_conv3x3_dgrad_workspace_bytes(N, H, W, Ci, Co)
-    if need == 0:
-        raise RuntimeError('conv3x3_dgrad: unsupported shape (Co % 32, Ci % 64, W % 8 must be 0)')
-    ws = _conv_workspace(dy.device, need)
-    dx = torch.empty((N, Ci, H, W), dtype=torch.float32, device=dy.device, memory_format=torch.channels_last)
-    rc = lib.t2o_conv3x3_dgrad_nhwc(_ptr(dy), _ptr(weight), _ptr(dx), _ptr(ws), ws.numel(), N, H, W, Ci, Co, _stream(dy.device))
-    _lib.check(rc, 't2o_conv3x3_dgrad_nhwc')
-    return dx
-
-
-def conv3x3s2_dgrad(dy, weight):
-    """Data gradient of conv2d(x, weight, None, stride 2, padding 1) for an even-sized x (t2o_conv3x3s2_dgrad_nhwc).
-    dy (N,Co,Ho,Wo) and weight (Co,Ci,3,3) channels-last; returns dx (N,Ci,2Ho,2Wo) channels-last."""
+def _conv_dgrad(who, dy, weight, stride, hint):
+    """The body of conv3x3_dgrad (stride 1) and conv3x3s2_dgrad (stride 2: dy is the strided side)."""
     _need_gpu(dy, weight)
     N, Co, Ho, Wo = dy.shape
     Ci = weight.shape[1]
     dy = dy.contiguous(memory_format=torch.channels_last)
     weight = weight.contiguous(memory_format=torch.channels_last)
     lib = _lib.load()
-    need = lib.t2o_conv3x3s2_dgrad_workspace_bytes(N, Ho, Wo, Ci, Co)
+    need = (lib.t2o_conv3x3_dgrad_workspace_bytes if stride == 1 else lib.t2o_conv3x3s2_dgrad_workspace_bytes)(N, Ho, Wo, Ci, Co)
     if need == 0:
-        raise RuntimeError('conv3x3s2_dgrad: unsupported shape (Co % 32, Ci % 64, Wo % 8 must be 0 -- or Ci = 3, Co = 32 / 64)')
+        raise RuntimeError('%s: unsupported shape (%s)' % (who, hint))
     ws = _conv_workspace(dy.device, need)
-    dx = torch.empty((N, Ci, 2 * Ho, 2 * Wo), dtype=torch.float32, device=dy.device, memory_format=torch.channels_last)
-    rc = lib.t2o_conv3x3s2_dgrad_nhwc(_ptr(dy), _ptr(weight), _ptr(dx), _ptr(ws), ws.numel(), N, Ho, Wo, Ci, Co, _stream(dy.device))
-    _lib.check(rc, 't2o_conv3x3s2_dgrad_nhwc')
+    dx = _nhwc_empty(N, Ci, stride * Ho, stride * Wo, dy.device)
+    name = 't2o_conv3x3_dgrad_nhwc' if stride == 1 else 't2o_conv3x3s2_dgrad_nhwc'
+    _lib.check(getattr(lib, name)(_ptr(dy), _ptr(weight), _ptr(dx), _ptr(ws), ws.numel(), N, Ho, Wo, Ci, Co, _stream(dy.device)), name)
     return dx
+
+
+def _conv_wgrad(who, x, dy, stride, hint):
+    """The body of conv3x3_wgrad (stride 1) and conv3x3s2_wgrad (stride 2): t2o_conv3x3_wgrad_acc_nhwc, not accumulating --
+    what the two stride-named entry points run."""
+    _need_gpu(x, dy)
+    N, Co, Ho, Wo = dy.shape
+    Ci = x.shape[1]
+    if stride == 2 and tuple(x.shape) != (N, Ci, 2 * Ho, 2 * Wo):
+        raise ValueError('%s: x must be (N, Ci, 2 Ho, 2 Wo)' % who)
+    x = x.contiguous(memory_format=torch.channels_last)
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    lib = _lib.load()
+    need = (lib.t2o_conv3x3_wgrad_workspace_bytes if stride == 1 else lib.t2o_conv3x3s2_wgrad_workspace_bytes)(N, Ho, Wo, Ci, Co)
+    if need == 0:
+        raise RuntimeError('%s: unsupported shape (%s)' % (who, hint))
+    ws = _conv_workspace(x.device, need)
+    dw = _nhwc_empty(Co, Ci, 3, 3, x.device)
+    rc = lib.t2o_conv3x3_wgrad_acc_nhwc(_ptr(x), _ptr(dy), _ptr(dw), _ptr(ws), ws.numel(), N, Ho, Wo, Ci, Co, stride, 0, _stream(x.device))
+    _lib.check(rc, 't2o_conv3x3_wgrad_acc_nhwc')
+    return dw
+
+
+def conv3x3_forward(x, weight, want_stats=False):
+    """conv2d(x, weight, None, 1, 1) on the fp32 matrix cores (t2o_conv3x3_fwd_nhwc).  x (N,Ci,H,W) and weight
+    (Co,Ci,3,3) channels-last; returns y (N,Co,H,W) channels-last.  want_stats: returns (y, stats) with stats
+    (rows, 2, Co) = per pixel tile the channels' sums and sums of squares of y (t2o_conv3x3_fwd_stats_nhwc), the
+    input of batch_norm_relu(..., partial=stats)."""
+    return _conv_fwd('conv3x3_forward', x, weight, 1, want_stats, 'Ci % 32, Co % 64, W % 8 must be 0')
+
+
+def conv3x3_dgrad(dy, weight):
+    """Data gradient of conv2d(x, weight, None, 1, 1) (t2o_conv3x3_dgrad_nhwc).  dy (N,Co,H,W) and weight (Co,Ci,3,3)
+    channels-last; returns dx (N,Ci,H,W) channels-last."""
+    return _conv_dgrad('conv3x3_dgrad', dy, weight, 1, 'Co % 32, Ci % 64, W % 8 must be 0')
+
+
+def conv3x3s2_dgrad(dy, weight):
+    """Data gradient of conv2d(x, weight, None, stride 2, padding 1) for an even-sized x (t2o_conv3x3s2_dgrad_nhwc).
+    dy (N,Co,Ho,Wo) and weight (Co,Ci,3,3) channels-last; returns dx (N,Ci,2Ho,2Wo) channels-last."""
+    return _conv_dgrad('conv3x3s2_dgrad', dy, weight, 2, 'Co % 32, Ci % 64, Wo % 8 must be 0 -- or Ci = 3, Co = 32 / 64')
 
 
 def conv3x3s2_forward(x, weight, want_stats=False):
     """conv2d(x, weight, None, stride 2, padding 1) for an even-sized x (t2o_conv3x3s2_fwd_nhwc).  x (N,Ci,2Ho,2Wo)
     and weight (Co,Ci,3,3) channels-last; returns y (N,Co,Ho,Wo) channels-last (want_stats: as conv3x3_forward)."""
-    _need_gpu(x, weight)
-    N, Ci, Hi, Wi = x.shape
-    Co = weight.shape[0]
-    if Hi % 2 or Wi % 2:
-        raise ValueError('conv3x3s2_forward: the image size must be even')
-    Ho, Wo = Hi // 2, Wi // 2
-    x = x.contiguous(memory_format=torch.channels_last)
-    weight = weight.contiguous(memory_format=torch.channels_last)
-    lib = _lib.load()
-    need = lib.t2o_conv3x3s2_fwd_workspace_bytes(N, Ho, Wo, Ci, Co)
-    if need == 0:
-        raise RuntimeError('conv3x3s2_forward: unsupported shape (Ci % 32, Co % 64, Wo % 8 must be 0)')
-    ws = _conv_workspace(x.device, need)
-    y = torch.empty((N, Co, Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    if want_stats:
-        stats = torch.empty((lib.t2o_conv3x3_fwd_stats_rows(N, Ho, Wo, Co, 2), 2, Co), dtype=torch.float32, device=x.device)
-        rc = lib.t2o_conv3x3_fwd_stats_nhwc(_ptr(x), _ptr(weight), _ptr(y), _ptr(stats), _ptr(ws), ws.numel(), N, Ho, Wo, Ci, Co, 2,
-                                            _stream(x.device))
-        _lib.check(rc, 't2o_conv3x3_fwd_stats_nhwc')
-        return y, stats
-    rc = lib.t2o_conv3x3s2_fwd_nhwc(_ptr(x), _ptr(weight), _ptr(y), _ptr(ws), ws.numel(), N, Ho, Wo, Ci, Co, _stream(x.device))
-    _lib.check(rc, 't2o_conv3x3s2_fwd_nhwc')
-    return y
+    return _conv_fwd('conv3x3s2_forward', x, weight, 2, want_stats, 'Ci % 32, Co % 64, Wo % 8 must be 0')
 
 
 def stem_forward(x, weight, want_stats=False):
@@ -645,22 +635,7 @@ def stem_wgrad(x, dy):
 def conv3x3s2_wgrad(x, dy):
     """Weight gradient of conv2d(x, w, None, stride 2, padding 1) (t2o_conv3x3s2_wgrad_nhwc).  x (N,Ci,2Ho,2Wo),
     dy (N,Co,Ho,Wo), both channels-last; returns dw (Co,Ci,3,3) channels-last."""
-    _need_gpu(x, dy)
-    N, Co, Ho, Wo = dy.shape
-    Ci = x.shape[1]
-    if tuple(x.shape) != (N, Ci, 2 * Ho, 2 * Wo):
-        raise ValueError('conv3x3s2_wgrad: x must be (N, Ci, 2 Ho, 2 Wo)')
-    x = x.contiguous(memory_format=torch.channels_last)
-    dy = dy.contiguous(memory_format=torch.channels_last)
-    lib = _lib.load()
-    need = lib.t2o_conv3x3s2_wgrad_workspace_bytes(N, Ho, Wo, Ci, Co)
-    if need == 0:
-        raise RuntimeError('conv3x3s2_wgrad: unsupported shape (channels must be multiples of 64, Wo a multiple of 4)')
-    ws = _conv_workspace(x.device, need)
-    dw = torch.empty((Co, Ci, 3, 3), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    rc = lib.t2o_conv3x3s2_wgrad_nhwc(_ptr(x), _ptr(dy), _ptr(dw), _ptr(ws), ws.numel(), N, Ho, Wo, Ci, Co, _stream(x.device))
-    _lib.check(rc, 't2o_conv3x3s2_wgrad_nhwc')
-    return dw
+    return _conv_wgrad('conv3x3s2_wgrad', x, dy, 2, 'channels must be multiples of 64, Wo a multiple of 4')
 
 
 def conv3x3s2_supported(x, weight, stride, padding):
@@ -678,15 +653,15 @@ def conv3x3s2_supported(x, weight, stride, padding):
 
 
 class _Conv3x3S2Fn(torch.autograd.Function):
-    """conv2d(x, w, 3x3, stride 2, padding 1) on the hand-written kernels: 'F' forward, 's' data gradient, 'S' weight
-    gradient in _CONV_OWN (a stem with an odd-sized image and gradients keeps the library call: its gradient kernels want an even image)."""
+    """conv2d(x, w, 3x3, stride 2, padding 1) on the hand-written kernels, all three directions (a stem with an odd-sized
+    image and gradients keeps the library call: its gradient kernels want an even image)."""
 
     @staticmethod
     def forward(ctx, x, weight, want_stats=False):
         ctx.save_for_backward(x, weight)
         even = x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
-        own = 'F' in _CONV_OWN and weight.shape[1] % 32 == 0 and weight.shape[0] % 64 == 0 and x.shape[3] % 16 == 0 and even
-        stem = 'T' in _CONV_OWN and weight.shape[1] == 3 and weight.shape[0] in (32, 64)
+        own = weight.shape[1] % 32 == 0 and weight.shape[0] % 64 == 0 and x.shape[3] % 16 == 0 and even
+        stem = weight.shape[1] == 3 and weight.shape[0] in (32, 64)
         fwd = conv3x3s2_forward if own else stem_forward if stem else None
         slow = (lambda: conv3x3_any_forward(x, weight, 2)) if weight.shape[1] % 32 == 0 else \
             (lambda: torch.nn.functional.conv2d(x, weight, None, 2, 1))
@@ -704,10 +679,10 @@ class _Conv3x3S2Fn(torch.autograd.Function):
         is_stem = weight.shape[1] == 3
         even = x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
         fast_d = even and (is_stem or dy.shape[3] % 8 == 0)
-        own = ctx.needs_input_grad[0] and 's' in _CONV_OWN and fast_d
-        own_w = (ctx.needs_input_grad[1] and 'S' in _CONV_OWN and weight.shape[0] % 64 == 0 and weight.shape[1] % 64 == 0
+        own = ctx.needs_input_grad[0] and fast_d
+        own_w = (ctx.needs_input_grad[1] and weight.shape[0] % 64 == 0 and weight.shape[1] % 64 == 0
                  and dy.shape[3] % 4 == 0 and even)
-        stem_w = ctx.needs_input_grad[1] and 'W' in _CONV_OWN and is_stem and weight.shape[0] in (32, 64)
+        stem_w = ctx.needs_input_grad[1] and is_stem and weight.shape[0] in (32, 64)
         any_d = ctx.needs_input_grad[0] and not own and not is_stem
         any_w = ctx.needs_input_grad[1] and not own_w and not stem_w and not is_stem
         mask = [ctx.needs_input_grad[0] and not own and not any_d, ctx.needs_input_grad[1] and not own_w and not stem_w and not any_w, False]
@@ -741,12 +716,6 @@ def conv3x3_supported(x, weight, stride, padding):
             and weight.shape[1] % 64 == 0 and x.is_contiguous(memory_format=torch.channels_last))
 
 
-# every direction of a supported layer runs on the own kernels (the letters name them: 'w' weight gradient, 'f' forward,
-# 'd' data gradient of the stride-1 layers; 'F' / 's' / 'S' the same for stride 2; 'T' forward and 'W' weight gradient
-# of the 3-channel stem).  Frozen since round 3 (was an A/B environment switch while the kernels were being written).
-_CONV_OWN = 'wfdFsSTW'
-
-
 def _own_direct(x):
     """The forward / data-gradient kernel wants W % 8 == 0 (a DMA piece of 8 pixels inside one image row)."""
     return x.shape[3] % 8 == 0
@@ -758,8 +727,8 @@ class _Conv3x3Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, want_stats=False):
         ctx.save_for_backward(x, weight)
-        own = 'f' in _CONV_OWN and _own_direct(x)
-        if want_stats:                                       # (y, stats); stats None where the any-size kernel computes y
+        own = _own_direct(x)
+        if want_stats:                                      # (y, stats); stats None where the any-size kernel computes y
             y, stats = conv3x3_forward(x, weight, True) if own else (conv3x3_any_forward(x, weight, 1), None)
             if stats is not None:
                 ctx.mark_non_differentiable(stats)
@@ -772,13 +741,13 @@ class _Conv3x3Fn(torch.autograd.Function):
         dy = dy.contiguous(memory_format=torch.channels_last)
         dx = None
         if ctx.needs_input_grad[0]:
-            if 'd' in _CONV_OWN and _own_direct(x):
+            if _own_direct(x):
                 dx = conv3x3_dgrad(dy, weight)
             else:
                 dx = conv3x3_any_dgrad(dy, weight, x.shape[2:], 1)
         dw = None
         if ctx.needs_input_grad[1]:
-            if 'w' in _CONV_OWN and x.shape[3] % 4 == 0:
+            if x.shape[3] % 4 == 0:
                 dw = conv3x3_wgrad(x, dy)
             else:
                 dw = conv3x3_any_wgrad(x, dy, 1)
@@ -961,12 +930,9 @@ def fused_sequence_l1_value_grad(img, ops, params, target, gloss=None, want_imag
     return loss, gimg, gparams, (out if want_image else None)
 
 
-def _planner_masks(lib, who, masks, mask_index, J, imgs):
+def _planner_masks(who, masks, mask_index, J, imgs):
     """The (masks, mask_index) keywords of the two planner calls, checked HERE so that a wrong plane or index is a Python
     error and never a GPU fault -> (planes or None, n_mask, ctypes index array)."""
-    for name in ('t2o_op_candidates_multi_l1_masked', 't2o_fit_multi_l1_adam_masked'):
-        if not hasattr(lib, name):
-            raise RuntimeError('%s: libt2onet_hip.so has no %s (a library without the masked planner kernels)' % (who, name))
     index = [-1] * J if mask_index is None else [int(k) for k in mask_index]
     if len(index) != J:
         raise ValueError('%s: one mask index per job (%d for %d jobs)' % (who, len(index), J))
@@ -996,7 +962,7 @@ def candidates_multi_l1(ops, img_index, imgs, target, params, masks=None, mask_i
     H, W = imgs.shape[-2:]
     lib = _lib.load()
     if masks is not None or mask_index is not None:
-        planes, n_mask, c_mask = _planner_masks(lib, 'candidates_multi_l1', masks, mask_index, J, imgs)
+        planes, n_mask, c_mask = _planner_masks('candidates_multi_l1', masks, mask_index, J, imgs)
     loss = torch.empty(J, C, dtype=torch.float32, device=imgs.device)
     ws = torch.empty(max(lib.t2o_candidates_multi_workspace_bytes(J, C, H, W), 4), dtype=torch.uint8, device=imgs.device)
     c_ops = (ctypes.c_int * J)(*[int(o) for o in ops])
@@ -1046,7 +1012,7 @@ def fit_multi_l1(ops, img_index, imgs, targets, target_index, params0, steps=300
     c_img = (ctypes.c_int * max(J, 1))(*[int(i) for i in img_index])
     c_tgt = (ctypes.c_int * max(J, 1))(*[int(i) for i in target_index])
     if masks is not None or mask_index is not None:
-        planes, n_mask, c_mask = _planner_masks(lib, 'fit_multi_l1', masks, mask_index, J, imgs)
+        planes, n_mask, c_mask = _planner_masks('fit_multi_l1', masks, mask_index, J, imgs)
         rc = lib.t2o_fit_multi_l1_adam_masked(c_ops, c_img, c_tgt, c_mask, J, _ptr(imgs), imgs.shape[0], _ptr(targets),
                                               targets.shape[0], _ptr(planes), n_mask, _ptr(params), _ptr(dist), _ptr(ws),
                                               ws.numel(), H, W, int(steps), float(lr), float(betas[0]), float(betas[1]),
@@ -1291,9 +1257,9 @@ def stem_planar(x, weight, dy=None, want='fwd', into=None):
 
 
 def _ld(t, what):
-    if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1) or t.stride(0) < t.shape[1]:
+    if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] != 1 and t.stride(0) < t.shape[1]):
         raise ValueError('%s must be a 2-D fp32 matrix with contiguous rows (a column slice of a larger one is fine)' % what)
-    return t.stride(0)
+    return max(t.stride(0), t.shape[1])                    # (one row: its stride is never used and may be anything, 0 after expand())
 
 
 def gemm(A, B, out=None, a_kmajor=False, b_kmajor=False, accumulate=False):
@@ -1301,7 +1267,9 @@ def gemm(A, B, out=None, a_kmajor=False, b_kmajor=False, accumulate=False):
     same bits on every machine -- the products the framework's BLAS used to pick a kernel for).  A is (M,K), or (K,M) with
     a_kmajor (a `dy^T x` product sums over the rows of both operands); B is (N,K) -- nn.Linear's weight layout -- or (K,N) with
     b_kmajor.  Operands and `out` may be column slices of larger matrices."""
-    _need_gpu(A, B)
+    _need_gpu(A, B, out)
+    if out is not None and out.device != A.device:
+        raise ValueError('gemm: out is on %s, the operands on %s' % (out.device, A.device))
     K, M = (A.shape[0], A.shape[1]) if a_kmajor else (A.shape[1], A.shape[0])
     Kb, N = (B.shape[0], B.shape[1]) if b_kmajor else (B.shape[1], B.shape[0])
     if K != Kb:
@@ -1324,14 +1292,16 @@ def gemm(A, B, out=None, a_kmajor=False, b_kmajor=False, accumulate=False):
 
 def colsum(X, out=None, accumulate=False):
     """out (N) [+]= the column sums of X (R,N) in a fixed order (t2o_colsum): bias gradients."""
-    _need_gpu(X)
+    _need_gpu(X, out)
     R, N = X.shape
     if out is None:
         out = torch.empty(N, dtype=torch.float32, device=X.device)
-    if R == 0:
-        return out if accumulate else out.zero_()
+    elif out.device != X.device:
+        raise ValueError('colsum: out is on %s, X on %s' % (out.device, X.device))
     if not (out.dim() == 1 and out.numel() == N and out.is_contiguous() and out.dtype == torch.float32):
         raise ValueError('colsum: out must be a dense fp32 vector of %d' % N)
+    if R == 0:
+        return out if accumulate else out.zero_()
     _lib.check(_lib.load().t2o_colsum(_ptr(X), _ptr(out), R, N, _ld(X, 'colsum: X'), 1 if accumulate else 0, _stream(X.device)), 't2o_colsum')
     return out
 
@@ -1647,16 +1617,11 @@ def wino_weight(w_taps_last, Cn, Ck):
     return U
 
 
-_OWN_WINO_GEMM = os.environ.get('T2O_WINO_GEMM', 'own') != 'lib'
-
-
 def gemm_nt_batched(A, B, M=None):
     """C[b] (M,N) = A[b][:M] @ B[b]^T for dense fp32 A (batches, rows >= M, K), B (batches, N, K): this library's matrix-core
-    kernel (t2o_gemm_nt_batched; N % 64 == 0, K % 32 == 0).  T2O_WINO_GEMM=lib: the framework's batched GEMM (A/B reference)."""
+    kernel (t2o_gemm_nt_batched; N % 64 == 0, K % 32 == 0)."""
     batches, rows, K = A.shape
     M = rows if M is None else M
-    if not _OWN_WINO_GEMM:
-        return torch.bmm(A[:, :M], B.transpose(1, 2))
     if A.stride(2) != 1 or A.stride(1) != K or A.stride(0) % K:
         raise ValueError('gemm_nt_batched: A must have dense rows (a row range of a larger (batches, R, K) tensor is fine)')
     rows = A.stride(0) // K                                # rows per plane of the tensor A lives in
@@ -1680,8 +1645,6 @@ def gemm_tn_batched(A, B):
     row ranges of larger tensors (the first passes of encoder.WgradArena's arenas)."""
     batches, rows, M = A.shape
     N = B.shape[2]
-    if not _OWN_WINO_GEMM:
-        return torch.bmm(A.transpose(1, 2), B).unsqueeze(0)
     lib = _lib.load()
     ldA, ldB = _plane_rows(A, 'gemm_tn_batched: A'), _plane_rows(B, 'gemm_tn_batched: B')
     splits = lib.t2o_gemm_tn_splits(batches, rows, M, N)
@@ -2006,6 +1969,31 @@ def replay_status(rc, what='t2o_replay_u8'):
     raise {1: ValueError, 2: NotImplementedError}.get(rc, RuntimeError)(msg)
 
 
+def _replay_args(who, src_u8, jobs, params, out):
+    """What replay_u8 and replay_u8_masked check alike, so that a wrong offset or size is a Python error and never a GPU fault:
+    the source, every job's (src_offset, out_offset, h, w, ...) against source and output, `out` (allocated to fit when None) and
+    params -> (jobs as tuples, out, contiguous params)."""
+    if not (torch.is_tensor(src_u8) and src_u8.is_cuda and src_u8.dtype == torch.uint8 and src_u8.is_contiguous()):
+        raise ValueError('%s: src must be a contiguous uint8 GPU tensor' % who)
+    jobs = [tuple(j) for j in jobs]
+    for j, (so, _, h, w) in enumerate(job[:4] for job in jobs):
+        if h > 0 and w > 0 and not (0 <= so and so + 3 * h * w <= src_u8.numel()):
+            raise ValueError('%s: job %d reads outside the %d-byte source' % (who, j, src_u8.numel()))
+    need = max([job[1] + 3 * job[2] * job[3] for job in jobs if job[2] > 0 and job[3] > 0] or [1])
+    if out is None:
+        out = torch.empty(need, dtype=torch.uint8, device=src_u8.device)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == src_u8.device):
+        raise ValueError('%s: out must be a contiguous uint8 GPU tensor on the source\'s device' % who)
+    elif out.numel() < need or any(job[1] < 0 for job in jobs):
+        raise ValueError('%s: a job writes outside the %d-byte output' % (who, out.numel()))
+    if params is not None:
+        _need_gpu(params)
+        params = params.contiguous()
+        if tuple(params.shape) != (len(jobs), REPLAY_MAX_STEPS, PARAM_PAD):
+            raise ValueError('%s: params must be (J, 8, 24), got %s' % (who, tuple(params.shape)))
+    return jobs, out, params
+
+
 def replay_u8(src_u8, jobs, params, out=None):
     """Apply known (operator, parameter) lists to uint8 (h,w,3) RGB pictures at their native size, bytes in and bytes out,
     in ONE launch (t2o_replay_u8): job j = (src_offset, out_offset, h, w, ops) reads its picture at byte src_offset of the
@@ -2013,24 +2001,7 @@ def replay_u8(src_u8, jobs, params, out=None):
     GPU; None when no job applies an operator) as Operator.execute does with specified_param, and writes at byte out_offset of
     `out` (allocated to fit when None).  The bytes equal resize_u8 at the picture's size -> operator_apply per step ->
     to_u8_hwc.  Returns out (1-D uint8)."""
-    if not (torch.is_tensor(src_u8) and src_u8.is_cuda and src_u8.dtype == torch.uint8 and src_u8.is_contiguous()):
-        raise ValueError('replay_u8: src must be a contiguous uint8 GPU tensor')
-    jobs = [tuple(j) for j in jobs]
-    for j, (so, oo, h, w, ops) in enumerate(jobs):
-        if h > 0 and w > 0 and not (0 <= so and so + 3 * h * w <= src_u8.numel()):
-            raise ValueError('replay_u8: job %d reads outside the %d-byte source' % (j, src_u8.numel()))
-    need = max([oo + 3 * h * w for _, oo, h, w, _ in jobs if h > 0 and w > 0] or [1])
-    if out is None:
-        out = torch.empty(need, dtype=torch.uint8, device=src_u8.device)
-    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == src_u8.device):
-        raise ValueError('replay_u8: out must be a contiguous uint8 GPU tensor on the source\'s device')
-    elif out.numel() < need or any(oo < 0 for _, oo, _, _, _ in jobs):
-        raise ValueError('replay_u8: a job writes outside the %d-byte output' % out.numel())
-    if params is not None:
-        _need_gpu(params)
-        params = params.contiguous()
-        if tuple(params.shape) != (len(jobs), REPLAY_MAX_STEPS, PARAM_PAD):
-            raise ValueError('replay_u8: params must be (J, 8, 24), got %s' % (tuple(params.shape),))
+    jobs, out, params = _replay_args('replay_u8', src_u8, jobs, params, out)
     rc = _lib.load().t2o_replay_u8(_ptr(src_u8), _ptr(out), replay_jobs(jobs), len(jobs), _ptr(params), _stream(src_u8.device))
     replay_status(rc)
     return out
@@ -2057,37 +2028,19 @@ def replay_u8_masked(src_u8, jobs, params, masks_u8, mask_offsets, out=None):
     computes clamp(o * m + x * (1 - m), 0, 1) with m = byte / 255 where it names a mask, clamp(o, 0, 1) where it names
     none.  The bytes equal resize_u8 at the picture's size -> operator_apply(op, x, param, mask (1,1,h,w) fp32) per step ->
     to_u8_hwc.  Returns out (1-D uint8)."""
-    if not (torch.is_tensor(src_u8) and src_u8.is_cuda and src_u8.dtype == torch.uint8 and src_u8.is_contiguous()):
-        raise ValueError('replay_u8_masked: src must be a contiguous uint8 GPU tensor')
+    jobs, out, params = _replay_args('replay_u8_masked', src_u8, jobs, params, out)
     mask_offsets = [int(o) for o in mask_offsets]
     if len(mask_offsets) > REPLAY_MAX_MASKS:
         raise ValueError('replay_u8_masked: at most 4 masks per launch, got %d' % len(mask_offsets))
     if mask_offsets and not (torch.is_tensor(masks_u8) and masks_u8.is_cuda and masks_u8.dtype == torch.uint8
                              and masks_u8.is_contiguous() and masks_u8.device == src_u8.device):
         raise ValueError('replay_u8_masked: masks must be a contiguous uint8 GPU tensor on the source\'s device')
-    jobs = [tuple(j) for j in jobs]
-    for j, (so, oo, h, w, ops, mask_of) in enumerate(jobs):
+    for j, (_, _, h, w, ops, mask_of) in enumerate(jobs):
         if len(mask_of) > len(ops):
             raise ValueError('replay_u8_masked: job %d names %d masks for %d steps' % (j, len(mask_of), len(ops)))
-        if not (h > 0 and w > 0):
-            continue                                             # the library refuses it
-        if not (0 <= so and so + 3 * h * w <= src_u8.numel()):
-            raise ValueError('replay_u8_masked: job %d reads outside the %d-byte source' % (j, src_u8.numel()))
-        for i in mask_of:
+        for i in mask_of if h > 0 and w > 0 else ():             # (an empty picture: the library refuses it)
             if 0 <= i < len(mask_offsets) and not (0 <= mask_offsets[i] and mask_offsets[i] + h * w <= masks_u8.numel()):
                 raise ValueError('replay_u8_masked: job %d reads mask %d outside the %d-byte mask buffer' % (j, i, masks_u8.numel()))
-    need = max([oo + 3 * h * w for _, oo, h, w, _, _ in jobs if h > 0 and w > 0] or [1])
-    if out is None:
-        out = torch.empty(need, dtype=torch.uint8, device=src_u8.device)
-    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == src_u8.device):
-        raise ValueError('replay_u8_masked: out must be a contiguous uint8 GPU tensor on the source\'s device')
-    elif out.numel() < need or any(j[1] < 0 for j in jobs):
-        raise ValueError('replay_u8_masked: a job writes outside the %d-byte output' % out.numel())
-    if params is not None:
-        _need_gpu(params)
-        params = params.contiguous()
-        if tuple(params.shape) != (len(jobs), REPLAY_MAX_STEPS, PARAM_PAD):
-            raise ValueError('replay_u8_masked: params must be (J, 8, 24), got %s' % (tuple(params.shape),))
     offs = (ctypes.c_longlong * max(len(mask_offsets), 1))(*mask_offsets)
     rc = _lib.load().t2o_replay_u8_masked(_ptr(src_u8), _ptr(out), replay_jobs([j[:5] for j in jobs]), replay_mask_table(jobs),
                                           len(jobs), _ptr(params), _ptr(masks_u8) if mask_offsets else None, offs,
@@ -2181,13 +2134,7 @@ def mask_select(planes, slot, pred_op):
     """Actor.get_gt_mask from device values (t2o_mask_select): planes (N,H,W) uint8, slot (B,V) int32 -- a plane number or
     -1 --, pred_op (B,) or (B,1) int64, all on the GPU -> (B,1,H,W) fp32 = float(planes[slot[b][pred_op[b]]]), all ones where
     the slot is -1 or the operator lies outside [0, V): no entry means a global edit.  One launch, no host read."""
-    if not (planes.is_cuda and planes.dtype == torch.uint8 and planes.dim() == 3 and planes.is_contiguous()):
-        raise RuntimeError('mask_select: planes must be a contiguous (N,H,W) uint8 GPU tensor; there is no CPU implementation')
-    if not (slot.is_cuda and slot.dtype == torch.int32 and slot.dim() == 2 and slot.is_contiguous()):
-        raise RuntimeError('mask_select: slot must be a contiguous (B,V) int32 GPU tensor')
-    pred_op = pred_op.reshape(-1)
-    if not (pred_op.is_cuda and pred_op.dtype == torch.int64 and pred_op.is_contiguous() and pred_op.numel() == slot.shape[0]):
-        raise RuntimeError('mask_select: pred_op must be a contiguous int64 GPU tensor of B elements')
+    pred_op = _plane_args('mask_select', planes, slot, pred_op)
     N, H, W = planes.shape
     B, V = slot.shape
     out = torch.empty(B, 1, H, W, dtype=torch.float32, device=planes.device)
@@ -2203,17 +2150,17 @@ pred_op (B,) or (B,1) int64 the operator vocabulary id each sample chose.  Execu
 apply_planes then reads the bytes where they lie instead of a (B,1,H,W) fp32 tensor from mask_select."""
 
 
-def _plane_args(planes, slot, pred_op, img):
-    """The argument checks of mask_select, plus the image's shape."""
+def _plane_args(who, planes, slot, pred_op, img=None):
+    """The argument checks of mask_select and apply_planes (which also has the images they must belong to) -> pred_op (B,)."""
     if not (planes.is_cuda and planes.dtype == torch.uint8 and planes.dim() == 3 and planes.is_contiguous()):
-        raise RuntimeError('apply_planes: planes must be a contiguous (N,H,W) uint8 GPU tensor; there is no CPU implementation')
+        raise RuntimeError('%s: planes must be a contiguous (N,H,W) uint8 GPU tensor; there is no CPU implementation' % who)
     if not (slot.is_cuda and slot.dtype == torch.int32 and slot.dim() == 2 and slot.is_contiguous()):
-        raise RuntimeError('apply_planes: slot must be a contiguous (B,V) int32 GPU tensor')
+        raise RuntimeError('%s: slot must be a contiguous (B,V) int32 GPU tensor' % who)
     pred_op = pred_op.detach().reshape(-1)
     if not (pred_op.is_cuda and pred_op.dtype == torch.int64 and pred_op.is_contiguous() and pred_op.numel() == slot.shape[0]):
-        raise RuntimeError('apply_planes: pred_op must be a contiguous int64 GPU tensor of B elements')
-    if slot.shape[0] != img.shape[0] or tuple(planes.shape[1:]) != tuple(img.shape[2:]):
-        raise ValueError('apply_planes: planes %s / slot %s do not belong to images %s' % (tuple(planes.shape), tuple(slot.shape), tuple(img.shape)))
+        raise RuntimeError('%s: pred_op must be a contiguous int64 GPU tensor of B elements' % who)
+    if img is not None and (slot.shape[0] != img.shape[0] or tuple(planes.shape[1:]) != tuple(img.shape[2:])):
+        raise ValueError('%s: planes %s / slot %s do not belong to images %s' % (who, tuple(planes.shape), tuple(slot.shape), tuple(img.shape)))
     return pred_op
 
 
@@ -2229,7 +2176,7 @@ class _ApplyPlanesFn(torch.autograd.Function):
         img = _img(img)
         param = param.contiguous()
         op_id = op_id.contiguous()
-        pred_op = _plane_args(planes, slot, pred_op, img)
+        pred_op = _plane_args('apply_planes', planes, slot, pred_op, img)
         B, _, H, W = img.shape
         if param.shape != (B, PARAM_PAD):
             raise ValueError('param must be (B,24)')
@@ -2301,14 +2248,7 @@ _feather_ws = {}
 def _feather_workspace(need, device):
     """The intermediate of feather_u8: cached per device and stream like _scratch, but a buffer of its own -- a 24 Mpx plane
     needs 48 MB, which the shared scratch should not be grown to."""
-    if torch.cuda.is_current_stream_capturing():
-        return torch.empty(max(need, 8), dtype=torch.uint8, device=device)
-    key = (device.index, _stream(device))
-    ws = _feather_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
-        _feather_ws[key] = ws
-    return ws
+    return _scratch(need, device, _feather_ws, 8)
 
 
 def feather_u8(buffer, jobs, out=None):

@@ -220,8 +220,8 @@ int emul_fused_bwd(const int* ops, int K, const float* img, const float* params,
         const bool st2 = use_static && vec == 1 && emu_chain_is<EmuSeq2>(a), st5 = use_static && vec == 1 && emu_chain_is<EmuSeq5>(a);
         for (int blk = 0; blk < nblk; ++blk)
           for (int tid = 0; tid < kThreads; ++tid) {
-            if (st2) { if (last) l1_total += chain_bwd_thread_static<true, EmuSeq2, false>(a, b, blk, tid, tab.data(), sv.data(), acc); else chain_bwd_thread_static<false, EmuSeq2, false>(a, b, blk, tid, tab.data(), sv.data(), acc); }
-            else if (st5) { if (last) l1_total += chain_bwd_thread_static<true, EmuSeq5, false>(a, b, blk, tid, tab.data(), sv.data(), acc); else chain_bwd_thread_static<false, EmuSeq5, false>(a, b, blk, tid, tab.data(), sv.data(), acc); }
+            if (st2) { if (last) l1_total += chain_bwd_thread_static<true, EmuSeq2>(a, b, blk, tid, tab.data(), acc); else chain_bwd_thread_static<false, EmuSeq2>(a, b, blk, tid, tab.data(), acc); }
+            else if (st5) { if (last) l1_total += chain_bwd_thread_static<true, EmuSeq5>(a, b, blk, tid, tab.data(), acc); else chain_bwd_thread_static<false, EmuSeq5>(a, b, blk, tid, tab.data(), acc); }
             else if (vec == 2) { if (last) l1_total += chain_bwd_thread<2, true>(a, b, blk, tid, tab.data(), sv.data(), acc); else chain_bwd_thread<2, false>(a, b, blk, tid, tab.data(), sv.data(), acc); }
             else { if (last) l1_total += chain_bwd_thread<1, true>(a, b, blk, tid, tab.data(), sv.data(), acc); else chain_bwd_thread<1, false>(a, b, blk, tid, tab.data(), sv.data(), acc); }
           }

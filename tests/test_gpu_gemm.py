@@ -70,6 +70,19 @@ def test_gemm_rejects_bad_arguments():
         T.gemm(A, torch.zeros(5, 6, device=DEV), out=torch.zeros(4, 4, device=DEV))
     with pytest.raises(RuntimeError):
         T.gemm(torch.zeros(4, 6), torch.zeros(5, 6))        # host tensors: no CPU fallback
+    B = synth.uniform((5, 6), 12, -1.0, 1.0).to(DEV)
+    with pytest.raises(RuntimeError):
+        T.gemm(A, B, out=torch.zeros(4, 5))                 # a host `out`: an error here, not a fault in the kernel
+    with pytest.raises(RuntimeError):
+        T.colsum(A, out=torch.zeros(6))
+    with pytest.raises(RuntimeError):
+        T.colsum(torch.zeros(0, 6, device=DEV), out=torch.zeros(6))     # (checked before the empty matrix returns)
+    # one row: its stride is never used, so any value is legal -- what expand() gives it, or 0
+    row = synth.uniform((6,), 11, -1.0, 1.0).to(DEV)
+    for A1 in (torch.zeros(6, device=DEV).expand(1, 6), row.expand(1, 6), row.as_strided((1, 6), (0, 1))):
+        ref = A1.double() @ B.double().t()
+        tol = 2e-6 * max(1.0, float(ref.abs().max()))
+        np.testing.assert_allclose(T.gemm(A1, B).cpu().numpy(), ref.cpu().numpy(), rtol=1e-5, atol=tol * (6 ** 0.5))
 
 
 def test_lstm_layer_and_tape_launch_no_library_gemm():

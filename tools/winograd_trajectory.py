@@ -1,5 +1,5 @@
 """Do the Winograd layers change training?  The same 40 deterministic (arg-max) episode train steps at bs=64 256x256 with the
-direct kernels everywhere (T2O_WINOGRAD=0) and with Winograd F(2x2,3x3) on the 256- / 512-channel layers (default), each in
+direct kernels everywhere (encoder._WINOGRAD = False in the worker) and with Winograd F(2x2,3x3) on the 256- / 512-channel layers (default), each in
 its own process; prints both loss curves and their deviation.  python tools/winograd_trajectory.py [steps]"""
 import json, os, subprocess, sys
 
@@ -12,6 +12,9 @@ import t2onet_amd
 from t2onet_amd.actor import Actor
 from t2onet_amd.train import Trainer
 import bench
+if sys.argv[2] == 'direct':
+    import t2onet_amd.encoder
+    t2onet_amd.encoder._WINOGRAD = False
 dev = torch.device('cuda:0')
 opt = t2onet_amd.default_options()
 torch.manual_seed(10)
@@ -31,9 +34,8 @@ print(json.dumps(out))
 
 steps = sys.argv[1] if len(sys.argv) > 1 else '40'
 curves = {}
-for name, env in (('direct', {'T2O_WINOGRAD': '0'}), ('winograd', {})):
-    e = dict(os.environ); e.update(env)
-    r = subprocess.run([sys.executable, '-c', WORKER, steps], env=e, capture_output=True, text=True)
+for name in ('direct', 'winograd'):
+    r = subprocess.run([sys.executable, '-c', WORKER, steps, name], capture_output=True, text=True)
     if r.returncode:
         sys.stderr.write(r.stderr[-2000:]); sys.exit(1)
     curves[name] = json.loads(r.stdout.strip().splitlines()[-1])
