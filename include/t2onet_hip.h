@@ -749,6 +749,24 @@ int t2o_resize_u8_to_f32(const unsigned char* src, const t2o_image_desc_t* descs
                          void* stream);
 int t2o_f32_to_u8_hwc(const float* img, int n, int h, int w, unsigned char* out, void* stream);
 
+/* ---- a training batch out of a device-resident set of 8-bit pictures (t2o_resident.hip).  store: DEVICE bytes, 16-byte
+ * aligned, holding the set after its resize: item i of N has up to K <= 8 pictures, picture (i, k) being (h,w,3) uint8
+ * RGB in HWC order at store + slot_offsets[i * K + k]; slot_offsets: DEVICE (N, K) int64, every offset a multiple of 16
+ * (the kernel reads a slot as aligned dwords), -1 = item i has no picture k.  index: DEVICE (B) int64, the batch's
+ * items; it is read ON THE DEVICE, so a captured launch serves another batch once the caller has overwritten it;
+ * indices may repeat.  For b < B and i = index[b]: out_x[b] = picture (i, 0) and out_ys[b, k - 1] = picture (i, k),
+ * k = 1 .. K - 1, each .astype(float32).transpose(2,0,1) / 255 -- the values the resize entry above writes for a source
+ * of the output's size, bit for bit; an absent picture gives zeros (the unused steps of a planned sequence, like the
+ * h = w = 0 descriptor).  out_x: (B,3,h,w) fp32; out_ys: (B,K-1,3,h,w) fp32, may be NULL when K = 1; any h, w.
+ * One launch; every output element is written exactly once; no atomics, no allocation, no host synchronisation,
+ * deterministic, capturable.
+ * The caller guarantees 0 <= index[b] < N and that every slot lies inside store: both tables live on the device and are
+ * not read back (an index outside [0, N) is treated as an item without pictures: nothing is read through it).
+ * T2O_EINVAL, before any launch: null pointers; N, K, B, h or w not positive; K > 8; a store that is not 16-byte, tables
+ * that are not 8-byte or outputs that are not 4-byte aligned; more than 2^31 - 1 workgroups (B K ceil(h w / 1024)). */
+int t2o_gather_u8_to_f32(const unsigned char* store, const long long* slot_offsets, const long long* index, int N, int K,
+                         int B, int h, int w, float* out_x, float* out_ys, void* stream);
+
 /* ---- a known operator list replayed on 8-bit pictures at their native size, 8-bit in and 8-bit out (t2o_replay.hip):
  * what an edit's decision, taken on a bounded proxy, costs on the original photo.  Job j reads the (h,w,3) uint8 RGB
  * picture at src + src_offset (any byte alignment; several jobs may name the same source) and writes (h,w,3) uint8 at

@@ -264,6 +264,122 @@ class DeviceBatches(object):
             yield device_batch(batch, **self.kw)
 
 
+RESIDENT_MAX_WORKERS = 16
+
+
+def resident_slot_bytes(size):
+    """Bytes between two slots of a resident store of size x size pictures: 3 S S rounded up to the 16-byte boundary every
+    slot starts on (functional.gather_u8 reads a slot as aligned dwords)."""
+    return (3 * size * size + 15) // 16 * 16
+
+
+def epoch_order(n, seed, epoch, rank=0, world=1):
+    """The items rank `rank` of `world` visits in `epoch`, in order: torch.randperm(n) seeded with seed + epoch, made on
+    the host; rank r takes every world-th one from the r-th on, all ranks cut to the same n // world."""
+    perm = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed) + int(epoch)))
+    return perm[rank::world][:n // world].contiguous()
+
+
+class ResidentFiveK(object):
+    """The whole training split of a FiveKAct(..., raw=True) on the device, resized once, served as batches by index.
+
+    Build (once, in __init__): a DataLoader of collate_raw chunks (the workers only decode), per chunk one upload
+    (functional.upload_packed), the resize launch to (n,3,S,S) fp32 and functional.to_u8_hwc into the store -- byte for
+    byte what a batch's resize would hold: trunc((b / 255) * 255) = b for all 256 bytes in fp32.  Kept: the store (N x 7
+    slots of resident_slot_bytes(S), dense, on the device), the (N,7) slot table (on the device; -1 = an unused step) and
+    the items' small tensors and request strings on the host (the train loop reads lengths there).
+
+    Iterating yields, per batch, [img_x, img_ys, req_idx, ops, params, reqs] equal to
+    device_batch(collate_raw(items), S, images_only=True) for the same items in the same order: one small non-blocking
+    index upload from pinned memory and one functional.gather_u8 launch; no picture crosses the bus and nothing waits on
+    the host.  The order of epoch e is epoch_order(N, seed, e, rank, world); every rank holds the whole set.  Each
+    iter() serves the next epoch.
+
+    memory_limit: bytes the store may take; default half of the device's free memory.  A larger store is refused with a
+    ValueError before anything is allocated or decoded."""
+
+    K = OP_MAX_LEN + 2
+
+    def __init__(self, dataset, size, batch_size, device=None, seed=0, rank=0, world=1, drop_last=True, num_workers=4,
+                 chunk_items=16, memory_limit=None):
+        from torch.utils.data import DataLoader
+        from . import functional as T
+        import time
+        if not getattr(dataset, 'raw', False):
+            raise ValueError('ResidentFiveK: the dataset must hand out decoded bytes (FiveKAct(..., raw=True))')
+        if size <= 0 or batch_size <= 0 or world <= 0 or not 0 <= rank < world:
+            raise ValueError('ResidentFiveK: size, batch_size and world must be positive and 0 <= rank < world')
+        tik = time.time()
+        if device is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        device = torch.device(device)
+        N, K, S = len(dataset), self.K, int(size)
+        if N == 0:
+            raise ValueError('ResidentFiveK: empty dataset')
+        slot = resident_slot_bytes(S)
+        self.nbytes = N * K * slot
+        limit = torch.cuda.mem_get_info(device)[0] // 2 if memory_limit is None else int(memory_limit)
+        if self.nbytes > limit:
+            raise ValueError('ResidentFiveK: %d items at %d x %d need a store of %d bytes, more than the %d allowed (half of the '
+                             "device's free memory unless memory_limit says otherwise); train without --resident"
+                             % (N, S, S, self.nbytes, limit))
+        self.size, self.batch_size, self.device, self.seed = S, int(batch_size), device, int(seed)
+        self.rank, self.world, self.drop_last, self.epoch = int(rank), int(world), bool(drop_last), 0
+        self.store = torch.zeros(self.nbytes, dtype=torch.uint8, device=device)
+        cells = self.store.view(N, K, slot)[:, :, :3 * S * S]
+        slots = torch.arange(N * K, dtype=torch.int64).view(N, K) * slot
+        loader = DataLoader(dataset, batch_size=int(chunk_items), shuffle=False, collate_fn=collate_raw, pin_memory=True,
+                            num_workers=max(0, min(int(num_workers), RESIDENT_MAX_WORKERS)))
+        rest, at = [], 0
+        for chunk in loader:
+            m = chunk['items']
+            dev_buffer, table_ptr, descs, keep = T.upload_packed(chunk['buffer'], chunk['descs'], device)
+            if descs.size != m * K:
+                raise ValueError('ResidentFiveK: an item must hold %d pictures (FiveKAct)' % K)
+            u8 = T.to_u8_hwc(T._resize_launch(dev_buffer, table_ptr, m * K, S, S)).view(m * K, -1)
+            cells[at:at + m, 0] = u8[:m]                                   # collate_raw's order: every img_x, then 6 img_ys per item
+            cells[at:at + m, 1:] = u8[m:].view(m, K - 1, -1)
+            absent = torch.from_numpy(np.ascontiguousarray(descs['h'] == 0))
+            slots[at:at + m, 0][absent[:m]] = -1
+            slots[at:at + m, 1:][absent[m:].view(m, K - 1)] = -1
+            rest.append(chunk['rest'])
+            at += m
+        self.slots = slots.to(device)
+        self.req_idx, self.ops, self.params = (torch.cat([r[j] for r in rest]) for j in range(3))
+        self.reqs = [s for r in rest for s in r[3]]
+        torch.cuda.synchronize(device)
+        self.build_seconds = time.time() - tik
+
+    def __len__(self):
+        n = len(self.reqs) // self.world
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def batch_indices(self, epoch):
+        """The (host, int64) item numbers of every batch of `epoch` on this rank, in order."""
+        order = epoch_order(len(self.reqs), self.seed, epoch, self.rank, self.world)
+        return [order[i * self.batch_size:(i + 1) * self.batch_size] for i in range(len(self))]
+
+    def fetch(self, idx, staged=None):
+        """One batch for the host int64 item numbers `idx`; staged: the same numbers in pinned memory (else they are pinned here)."""
+        from . import functional as T
+        if staged is None:
+            staged = idx.pin_memory()
+        index = staged.to(self.device, non_blocking=True)
+        img_x, img_ys = T.gather_u8(self.store, self.slots, index, self.size)
+        return [img_x, img_ys, self.req_idx[idx], self.ops[idx], self.params[idx], [self.reqs[i] for i in idx.tolist()]]
+
+    def __iter__(self):
+        epoch, self.epoch = self.epoch, self.epoch + 1
+        batches = self.batch_indices(epoch)
+        if not batches:
+            return
+        staged = torch.cat(batches).pin_memory()                           # the epoch's indices: one pinned block, a slice per batch
+        at = 0
+        for idx in batches:
+            yield self.fetch(idx, staged[at:at + idx.numel()])
+            at += idx.numel()
+
+
 class SyntheticFiveK(Dataset):
     """FiveK-shaped random items: what bench.py and the tests train on."""
 

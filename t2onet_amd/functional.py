@@ -1938,6 +1938,51 @@ def to_u8_hwc(t, out=None):
     return out.view(N, H, W, 3)
 
 
+# ---- resident set (t2o_resident.hip): a batch gathered out of a device-resident store of resized 8-bit pictures ----
+
+GATHER_MAX_K = 8
+
+
+def _need_gpu_as(t, dtype, what):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise RuntimeError('t2onet_amd: %s must be a contiguous %s tensor on the GPU (got %s on %s); there is no CPU '
+                           'implementation' % (what, dtype, getattr(t, 'dtype', type(t)), getattr(t, 'device', 'the host')))
+
+
+def gather_u8(store, slots, index, size, out=None):
+    """The pictures of the items `index` names out of a resident store, as the loaders' fp32 tensors: (img_x (B,3,h,w),
+    img_ys (B,K-1,3,h,w)), each picture .astype(float32).transpose(2,0,1) / 255, an absent one zeros.
+    store: 1-D uint8 GPU tensor; slots: (N,K) int64 GPU tensor, the byte offset of picture (i, k) in the store -- a
+    multiple of 16 -- or -1; index: (B,) int64 GPU tensor, read on the device (values in [0, N): the caller's promise,
+    nothing reads them back); size: int or (h, w), the pictures' size.  out: an (img_x, img_ys) pair to write into -- a
+    captured launch keeps serving new batches through the same three tensors.  One launch on the current stream."""
+    _need_gpu_as(store, torch.uint8, 'store')
+    _need_gpu_as(slots, torch.int64, 'slots')
+    _need_gpu_as(index, torch.int64, 'index')
+    h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    if store.dim() != 1 or slots.dim() != 2 or index.dim() != 1 or index.numel() == 0 or h <= 0 or w <= 0:
+        raise ValueError('gather_u8: store (bytes,), slots (N,K), index (B,) with B > 0, positive size')
+    N, K = slots.shape
+    if not 1 <= K <= GATHER_MAX_K or N == 0:
+        raise ValueError('gather_u8: slots must be (N,K) with N > 0 and 1 <= K <= %d' % GATHER_MAX_K)
+    B, dev = index.numel(), store.device
+    if slots.device != dev or index.device != dev:
+        raise ValueError('gather_u8: store, slots and index must lie on one device')
+    if out is None:
+        img_x = torch.empty(B, 3, h, w, dtype=torch.float32, device=dev)
+        img_ys = torch.empty(B, K - 1, 3, h, w, dtype=torch.float32, device=dev)
+    else:
+        img_x, img_ys = out
+        _need_gpu(img_x, img_ys)
+        if not (img_x.is_contiguous() and img_ys.is_contiguous() and img_x.device == dev and img_ys.device == dev
+                and tuple(img_x.shape) == (B, 3, h, w) and tuple(img_ys.shape) == (B, K - 1, 3, h, w)):
+            raise ValueError('gather_u8: out must be contiguous fp32 tensors of shapes %s and %s' % ((B, 3, h, w), (B, K - 1, 3, h, w)))
+    rc = _lib.load().t2o_gather_u8_to_f32(_ptr(store), _ptr(slots), _ptr(index), N, K, B, h, w, _ptr(img_x),
+                                          _ptr(img_ys) if K > 1 else None, _stream(dev))
+    _lib.check(rc, 't2o_gather_u8_to_f32')
+    return img_x, img_ys
+
+
 # ---- 8-bit replay (t2o_replay.hip): a known operator list on uint8 pictures at their native size ----
 
 REPLAY_MAX_JOBS, REPLAY_MAX_STEPS = 64, 8

@@ -15,6 +15,8 @@ GIER layout (train_GIER_seq2seqL1.py: gier.GIERDatasetAct for training, gier.GIE
 vocabularies; global edits unless --load_mask: the annotated regions' run lengths ride with each batch, one
 gier.MaskTable.from_rle per batch (one upload, one launch) and both train steps run their local operators under the masks,
 the operator kernels reading the uint8 planes in place; score such a checkpoint with gier_cli --load_mask).
+FiveK real data with --resident: the training split is decoded and resized ONCE into a device-resident uint8 store
+(data.ResidentFiveK); every batch after that is one index upload and one gather launch, no picture crosses the bus again.
 """
 import argparse
 import json
@@ -28,7 +30,7 @@ from torch.utils.data import DataLoader, DistributedSampler
 from . import default_options
 from .actor import Actor
 from . import evaluate
-from .data import DeviceBatches, FiveK, FiveKAct, SyntheticFiveK, collate_raw, device_batch
+from .data import DeviceBatches, FiveK, FiveKAct, ResidentFiveK, SyntheticFiveK, collate_raw, device_batch
 from .train import Trainer
 
 
@@ -96,7 +98,12 @@ def parse_args(argv=None):
                     help='validation through evaluate.test_on_device: one fused metrics launch per image, one host read per pass')
     ap.add_argument('--load_mask', action='store_true',
                     help='GIER: train local edits under their annotated masks (device-resident uint8 planes, read in place)')
+    ap.add_argument('--resident', action='store_true',
+                    help='FiveK real data: decode and resize the training split once into a device-resident uint8 store; a batch '
+                         'is then one index upload and one gather launch')
     args = ap.parse_args(argv)
+    if args.resident and (args.synthetic or args.dataset == 'GIER'):
+        ap.error('--resident keeps a FiveK tree on the device: neither --synthetic nor --dataset GIER')
     if args.load_mask and args.dataset != 'GIER':
         ap.error('--load_mask needs --dataset GIER: only GIER annotates regions')
     if args.session is None:
@@ -142,11 +149,17 @@ def main(argv=None):
                                          'rle' if args.load_mask else False, args.session, args.img_size), with_masks=args.load_mask)
     else:
         dataset = SyntheticFiveK(n=args.batch_size * 64, size=args.img_size) if args.synthetic else \
-            FiveKAct(args.img_dir, args.anno_dir, args.act_dir, 'train', 1, args.img_size, raw=raw)
-    sampler = DistributedSampler(dataset, world, rank, shuffle=True) if world > 1 else None
+            FiveKAct(args.img_dir, args.anno_dir, args.act_dir, 'train', 1, args.img_size, raw=raw or args.resident)
+    sampler = DistributedSampler(dataset, world, rank, shuffle=True) if world > 1 and not args.resident else None
     raw_kw = dict(collate_fn=collate_raw, pin_memory=True) if raw else {}
     loader = DataLoader(dataset, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler,
                         num_workers=args.num_workers, drop_last=True, **(dict(collate_fn=collate_masks) if args.load_mask else raw_kw))
+    if args.resident:                                                # the one-time build resizes on the device; every rank holds the set
+        loader = ResidentFiveK(dataset, args.img_size, args.batch_size, device, seed=args.manual_seed, rank=rank, world=world,
+                               num_workers=args.num_workers)
+        if rank == 0:
+            print('resident set: {} items, {} bytes on the device, built in {:.1f} s'.format(
+                len(dataset), loader.nbytes, loader.build_seconds), flush=True)
     if gier_run:
         val_loader = DataLoader(_Tuples(GIERDataset(args.data_dir, args.vocab_dir, 'val', args.data_mode, False, args.session)),
                                 batch_size=1, shuffle=False, num_workers=1)
@@ -171,7 +184,7 @@ def main(argv=None):
         for batch in loader:
             itr += 1
             tik = time.time()
-            if raw:                                                  # decoded bytes: one upload, one resize launch
+            if raw and not args.resident:                            # decoded bytes: one upload, one resize launch
                 batch = device_batch(batch, args.img_size, device, images_only=True)
             masks = None
             if args.load_mask:                                       # the batch's union planes: one upload, one launch
