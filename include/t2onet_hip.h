@@ -767,6 +767,21 @@ int t2o_f32_to_u8_hwc(const float* img, int n, int h, int w, unsigned char* out,
 int t2o_gather_u8_to_f32(const unsigned char* store, const long long* slot_offsets, const long long* index, int N, int K,
                          int B, int h, int w, float* out_x, float* out_ys, void* stream);
 
+/* ---- the same batch for ITEMS of up to 16 pictures that may share slots, with one row of a device table per sample
+ * (t2o_resident_items.hip; a GIER item: input, 8 planned steps, target, and the plane numbers of its local-edit masks).
+ * Pictures: the contract of t2o_gather_u8_to_f32 with K <= 16 -- the same thread program; for K <= 8 the outputs are
+ * bit-identical to that entry's.  A slot may appear in several items and several columns: a shared picture is stored once.
+ * rows: DEVICE (N, V) int32; out_rows: (B, V) int32 with out_rows[b][v] = rows[index[b]][v], all -1 for an index outside
+ * [0, N).  rows == NULL only together with V == 0 and out_rows == NULL (pictures only).  The rows are written by the SAME
+ * launch: ceil(B V / 256) workgroups appended to the flat grid of the pictures' B K ceil(h w / 1024).  Index and both
+ * tables are read on the device; every output element is written exactly once; no atomics, no allocation, no host
+ * synchronisation, deterministic, capturable.
+ * T2O_EINVAL, before any launch: the cases of t2o_gather_u8_to_f32 with K > 16 in place of K > 8; V < 0; rows, out_rows
+ * and V that do not agree; rows or out_rows not 4-byte aligned; more than 2^31 - 1 workgroups, the row workgroups included. */
+int t2o_gather_items_u8_to_f32(const unsigned char* store, const long long* slot_offsets, const long long* index, int N, int K,
+                               int B, int h, int w, float* out_x, float* out_ys, const int* rows, int V, int* out_rows,
+                               void* stream);
+
 /* ---- a known operator list replayed on 8-bit pictures at their native size, 8-bit in and 8-bit out (t2o_replay.hip):
  * what an edit's decision, taken on a bounded proxy, costs on the original photo.  Job j reads the (h,w,3) uint8 RGB
  * picture at src + src_offset (any byte alignment; several jobs may name the same source) and writes (h,w,3) uint8 at

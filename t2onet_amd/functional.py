@@ -1983,6 +1983,47 @@ def gather_u8(store, slots, index, size, out=None):
     return img_x, img_ys
 
 
+GATHER_ITEMS_MAX_K = 16
+
+
+def gather_items_u8(store, slots, index, size, rows=None, out=None):
+    """gather_u8 for items of up to 16 pictures whose slots may be shared between items (t2o_gather_items_u8_to_f32; for
+    K <= 8 the same bits as gather_u8), and with `rows` -- an (N,V) int32 GPU table -- also out_rows (B,V) int32 =
+    rows[index], written by the SAME launch (an index outside [0, N) gives a row of -1).  Returns (img_x, img_ys) or
+    (img_x, img_ys, out_rows).  out: the tensors to write into, a pair or, with rows, a triple."""
+    _need_gpu_as(store, torch.uint8, 'store')
+    _need_gpu_as(slots, torch.int64, 'slots')
+    _need_gpu_as(index, torch.int64, 'index')
+    if rows is not None:
+        _need_gpu_as(rows, torch.int32, 'rows')
+    h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    if store.dim() != 1 or slots.dim() != 2 or index.dim() != 1 or index.numel() == 0 or h <= 0 or w <= 0:
+        raise ValueError('gather_items_u8: store (bytes,), slots (N,K), index (B,) with B > 0, positive size')
+    N, K = slots.shape
+    if not 1 <= K <= GATHER_ITEMS_MAX_K or N == 0:
+        raise ValueError('gather_items_u8: slots must be (N,K) with N > 0 and 1 <= K <= %d' % GATHER_ITEMS_MAX_K)
+    B, dev = index.numel(), store.device
+    if rows is not None and (rows.dim() != 2 or rows.shape[0] != N or rows.shape[1] == 0):
+        raise ValueError('gather_items_u8: rows must be (N,V) with the N of slots and V > 0')
+    V = 0 if rows is None else rows.shape[1]
+    if slots.device != dev or index.device != dev or (rows is not None and rows.device != dev):
+        raise ValueError('gather_items_u8: store, slots, index and rows must lie on one device')
+    shapes = [(B, 3, h, w), (B, K - 1, 3, h, w)] + ([(B, V)] if V else [])
+    dtypes = [torch.float32, torch.float32, torch.int32]
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+    else:
+        out = tuple(out)
+        if len(out) != len(shapes) or not all(torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == d and t.is_contiguous()
+                                              and tuple(t.shape) == s for t, s, d in zip(out, shapes, dtypes)):
+            raise ValueError('gather_items_u8: out must be contiguous GPU tensors of shapes %s (fp32, fp32, int32)' % (shapes,))
+    rc = _lib.load().t2o_gather_items_u8_to_f32(_ptr(store), _ptr(slots), _ptr(index), N, K, B, h, w, _ptr(out[0]),
+                                                _ptr(out[1]) if K > 1 else None, _ptr(rows), V, _ptr(out[2]) if V else None,
+                                                _stream(dev))
+    _lib.check(rc, 't2o_gather_items_u8_to_f32')
+    return out
+
+
 # ---- 8-bit replay (t2o_replay.hip): a known operator list on uint8 pictures at their native size ----
 
 REPLAY_MAX_JOBS, REPLAY_MAX_STEPS = 64, 8

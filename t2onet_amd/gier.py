@@ -21,6 +21,9 @@ Two quirks of the reference, handled on purpose:
   * the dataset keys its mask_dict by int operator ids while get_gt_mask looks up str(op): a dict-path episode fed from
     the dataset never finds a mask.  MaskTable accepts both key types.
 load_mask_feature (h5 panoptic features) is out of scope.
+
+ResidentGIER (at the end) keeps the training items on the device: every distinct picture file and every distinct union
+plane once, a batch and its MaskTable by index in one launch (train_cli --resident_gier).
 """
 import copy
 import json
@@ -458,10 +461,11 @@ class GIERDatasetAct(GIERDataset):
     def collate(self, batch):
         return _collate(batch, arrays=True)
 
-    def get_act(self, item):
-        """(op_seq (op_max_len+2), params (op_max_len,24), imgs (op_max_len,3,S,S)): 'init distance' and the top
-        'operation sequence', truncated by data.analyze_traj (at most op_max_len = 8), colour / tone parameters divided by
-        their largest magnitude, a one-parameter value beyond +-5 replaced by 0."""
+    def get_plan(self, item):
+        """(op_seq (op_max_len+2), params (op_max_len,24), trunc_len, item_dir): 'init distance' and the top 'operation
+        sequence', truncated by data.analyze_traj (at most op_max_len = 8), colour / tone parameters divided by their
+        largest magnitude, a one-parameter value beyond +-5 replaced by 0; the pictures of the kept steps are
+        item_dir/edit{k}.jpg, k < trunc_len.  No picture is read."""
         pair_id = self.GIER.ReqId2PairId[item]
         data_id = self.GIER.op_data[pair_id]['input'].split('_')[0]
         item_dir = os.path.join(self.act_dir, '{}'.format(data_id))
@@ -484,6 +488,11 @@ class GIERDatasetAct(GIERDataset):
                 params[i, :n] = np.array(act[1])
         op_seq[0] = 1
         op_seq[len(seq) + 1] = 2
+        return op_seq, params, trunc_len, item_dir
+
+    def get_act(self, item):
+        """(op_seq, params, imgs (op_max_len,3,S,S)): get_plan and the pictures of its steps, zeros beyond the truncation."""
+        op_seq, params, trunc_len, item_dir = self.get_plan(item)
         imgs = torch.zeros(self.op_max_len, 3, self.train_img_size, self.train_img_size, dtype=torch.float32)
         for i in range(trunc_len):
             imgs[i] = D.load_image(os.path.join(item_dir, 'edit{}.jpg'.format(i)), self.train_img_size)
@@ -525,3 +534,162 @@ def collate_masks(batch):
     item to item, so the dicts cannot be merged key by key)."""
     from torch.utils.data import default_collate
     return tuple(default_collate([item[:-1] for item in batch])) + ([item[-1] for item in batch],)
+
+
+# ------------------------------------------------------------------ the training set on the device
+RESIDENT_UNION_JOBS = 65535                      # planes per functional.rle_union_u8 launch of the build
+
+
+class _Files(Dataset):
+    """Decoded pictures by path: all a worker of the resident build does."""
+
+    def __init__(self, paths):
+        self.paths = paths
+
+    def __len__(self):
+        return len(self.paths)
+
+    def __getitem__(self, i):
+        return D.decode_image(self.paths[i])
+
+
+def _collate_files(images):
+    """A chunk of decoded pictures as data.collate_raw packs them: one byte buffer headed by its descriptor table, and the
+    table as an (n,4) int32 tensor."""
+    from . import functional as T
+    buffer, descs = T.pack_u8(images, pin=False)
+    return buffer, torch.from_numpy(descs.view(np.int32).reshape(-1, 4).copy())
+
+
+class ResidentGIER(D.ResidentFiveK):
+    """The training items of a GIERDatasetAct (phase 'train') on the device, served as batches by index: the GIER form of
+    data.ResidentFiveK, whose epoch order, sharding and index staging it keeps (batch_indices, __iter__, __len__).
+
+    Pictures.  GIER has one item per REQUEST: the requests of a pair share all ten pictures, pairs on one input share the
+    input and the planned steps of act_dir/<data_id>.  The store holds ONE slot of data.resident_slot_bytes(S) per distinct
+    file path (uint8 HWC); .slots (N,10) int64 on the device names them per item -- column 0 the input, 1..8 the planned
+    steps (-1 at and beyond get_plan's truncation), 9 the target.  Build: workers decode in chunks; per chunk one upload,
+    the resize launch and functional.to_u8_hwc into the store (ResidentFiveK's path), so a gathered picture has the bits of
+    data.load_image(path, S).
+
+    Masks (a dataset made with is_load_mask='rle').  One uint8 (S,S) union plane per distinct (input name, mask ids),
+    .planes (P,S,S), written by functional.rle_union_u8 launches of at most 65535 jobs straight into the store; .rows
+    (N,V) int32 on the device holds, per item and operator vocabulary id, the plane's number or -1.  Without masks there
+    are neither planes nor rows.
+
+    fetch / iteration yield [img_x, img_ys (B,9,3,S,S), request_idx, ops, params, requests] -- what
+    collate_masks / the default collation of _Tuples(dataset) gives for the same items, the pictures on the device -- and,
+    with masks, a MaskTable(planes = the WHOLE plane store, slot = the items' rows) behind them: one small non-blocking
+    index upload and ONE functional.gather_items_u8 launch per batch, nothing uploaded or launched for the masks, every
+    shape the same for every batch.
+
+    memory_limit: bytes the set may take on the device (.nbytes: pictures, planes and both tables); default half of the
+    device's free memory.  A larger set is refused with a ValueError before anything is allocated or decoded.  Reports
+    .nbytes, .build_seconds, .n_pictures, .n_planes."""
+
+    K = OP_MAX_LEN + 2
+
+    def __init__(self, dataset, size, batch_size, device=None, seed=0, rank=0, world=1, drop_last=True, num_workers=4,
+                 chunk_pictures=64, memory_limit=None, n_vocab=None):
+        from torch.utils.data import DataLoader
+        from . import functional as T
+        import time
+        if not isinstance(dataset, GIERDatasetAct) or dataset.phase != 'train':
+            raise ValueError("ResidentGIER: the dataset must be a GIERDatasetAct in phase 'train'")
+        G = dataset.GIER
+        if G.is_load_mask not in (False, None, 'rle'):
+            raise ValueError("ResidentGIER: masks are built on the device from run lengths: is_load_mask must be False or 'rle'")
+        if size <= 0 or batch_size <= 0 or world <= 0 or not 0 <= rank < world or chunk_pictures <= 0:
+            raise ValueError('ResidentGIER: size, batch_size, chunk_pictures and world must be positive and 0 <= rank < world')
+        if int(size) != int(dataset.train_img_size):
+            raise ValueError('ResidentGIER: size %d is not the dataset\'s train_img_size %d' % (size, dataset.train_img_size))
+        tik = time.time()
+        if device is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        device = torch.device(device)
+        N, K, S = len(dataset), self.K, int(size)
+        if N == 0:
+            raise ValueError('ResidentGIER: empty dataset')
+        with_masks = G.is_load_mask == 'rle'
+        V = int(n_vocab) if n_vocab is not None else len(dataset.op_vocab2id)
+        # ---- the index, from the split and plan files alone: which files, which planes, which item uses which
+        paths, where, plans = [], {}, {}
+        plane_keys, plane_of = [], {}
+
+        def number(table, order, key):
+            at = table.get(key)
+            if at is None:
+                at = table[key] = len(order)
+                order.append(key)
+            return at
+        picture = np.full((N, K), -1, np.int64)
+        rows = np.full((N, V), -1, np.int32) if with_masks else None
+        req_idx, ops, params, reqs = [], [], [], []
+        for r in range(N):
+            pair_id = G.ReqId2PairId[r]
+            rec = G.op_data[pair_id]
+            name = rec['input'].split('_')[0]
+            if name not in plans:
+                plans[name] = dataset.get_plan(r)
+            op_seq, par, n, item_dir = plans[name]
+            picture[r, 0] = number(where, paths, os.path.join(G.img_dir, rec['input']))
+            for k in range(n):
+                picture[r, 1 + k] = number(where, paths, os.path.join(item_dir, 'edit{}.jpg'.format(k)))
+            picture[r, K - 1] = number(where, paths, os.path.join(G.img_dir, rec['output']))
+            req_idx.append(torch.tensor(_pad(G.getReqIdx[r].tolist())))
+            ops.append(torch.from_numpy(op_seq))
+            params.append(torch.from_numpy(par))
+            reqs.append(G.getReq[r])
+            if with_masks:
+                for op, ids in G.get_op_info(pair_id)[2].items():
+                    rows[r, MaskTable._key(op, V)] = number(plane_of, plane_keys, (name, tuple(int(i) for i in ids)))
+        slot = D.resident_slot_bytes(S)
+        self.n_pictures, self.n_planes = len(paths), len(plane_keys)
+        self.nbytes = self.n_pictures * slot + self.n_planes * S * S + picture.nbytes + (rows.nbytes if with_masks else 0)
+        limit = torch.cuda.mem_get_info(device)[0] // 2 if memory_limit is None else int(memory_limit)
+        if self.nbytes > limit:
+            raise ValueError('ResidentGIER: %d items at %d x %d (%d distinct pictures, %d mask planes) need %d bytes, more than the '
+                             "%d allowed (half of the device's free memory unless memory_limit says otherwise); train without "
+                             '--resident_gier' % (N, S, S, self.n_pictures, self.n_planes, self.nbytes, limit))
+        self.size, self.batch_size, self.device, self.seed = S, int(batch_size), device, int(seed)
+        self.rank, self.world, self.drop_last, self.epoch = int(rank), int(world), bool(drop_last), 0
+        # ---- the pictures: decode (workers), upload, resize, to bytes -- chunk by chunk into the store
+        self.store = torch.zeros(self.n_pictures * slot, dtype=torch.uint8, device=device)
+        cells = self.store.view(self.n_pictures, slot)[:, :3 * S * S]
+        loader = DataLoader(_Files(paths), batch_size=int(chunk_pictures), shuffle=False, collate_fn=_collate_files, pin_memory=True,
+                            num_workers=max(0, min(int(num_workers), D.RESIDENT_MAX_WORKERS)))
+        at = 0
+        for buffer, table in loader:
+            m = table.shape[0]
+            dev_buffer, table_ptr, descs, keep = T.upload_packed(buffer, table, device)
+            cells[at:at + m] = T.to_u8_hwc(T._resize_launch(dev_buffer, table_ptr, m, S, S)).view(m, -1)
+            at += m
+        self.slots = torch.from_numpy(np.where(picture >= 0, picture * slot, -1)).to(device)
+        # ---- the union planes: the annotated run lengths of a chunk of planes in one upload, one launch into the store
+        self.rows = self.planes = None
+        if with_masks:
+            self.planes = torch.zeros(self.n_planes, S, S, dtype=torch.uint8, device=device)
+            for c0 in range(0, self.n_planes, RESIDENT_UNION_JOBS):
+                files, masks, seen, jobs = {}, [], {}, []
+                for j, (name, ids) in enumerate(plane_keys[c0:c0 + RESIDENT_UNION_JOBS]):
+                    if name not in files:
+                        files[name] = G.load_mask_rles(name)
+                    sel = [number(seen, masks, (name, i)) for i in ids]
+                    jobs.append((sel, (c0 + j) * S * S, S, S))
+                T.rle_union_u8([files[name][i] for name, i in masks], jobs, device, out=self.planes.view(-1))
+            self.rows = torch.from_numpy(rows).to(device)
+        self.req_idx, self.ops, self.params, self.reqs = torch.stack(req_idx), torch.stack(ops), torch.stack(params), reqs
+        torch.cuda.synchronize(device)
+        self.build_seconds = time.time() - tik
+
+    def fetch(self, idx, staged=None):
+        """One batch for the host int64 item numbers `idx`; staged: the same numbers in pinned memory (else they are pinned here)."""
+        from . import functional as T
+        if staged is None:
+            staged = idx.pin_memory()
+        index = staged.to(self.device, non_blocking=True)
+        out = T.gather_items_u8(self.store, self.slots, index, self.size, rows=self.rows)
+        batch = [out[0], out[1], self.req_idx[idx], self.ops[idx], self.params[idx], [self.reqs[i] for i in idx.tolist()]]
+        if self.rows is not None:
+            batch.append(MaskTable(self.planes, out[2], (self.size, self.size)))
+        return batch

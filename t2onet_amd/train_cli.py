@@ -17,6 +17,9 @@ gier.MaskTable.from_rle per batch (one upload, one launch) and both train steps 
 the operator kernels reading the uint8 planes in place; score such a checkpoint with gier_cli --load_mask).
 FiveK real data with --resident: the training split is decoded and resized ONCE into a device-resident uint8 store
 (data.ResidentFiveK); every batch after that is one index upload and one gather launch, no picture crosses the bus again.
+GIER with --resident_gier: the same for the GIER training items (gier.ResidentGIER) -- every distinct picture file once in
+the store, and with --load_mask every distinct union plane once beside it; a batch, its MaskTable included, is one index
+upload and one launch.
 """
 import argparse
 import json
@@ -101,7 +104,13 @@ def parse_args(argv=None):
     ap.add_argument('--resident', action='store_true',
                     help='FiveK real data: decode and resize the training split once into a device-resident uint8 store; a batch '
                          'is then one index upload and one gather launch')
+    ap.add_argument('--resident_gier', action='store_true',
+                    help='GIER: decode and resize every distinct training picture once into a device-resident uint8 store, with '
+                         '--load_mask also every distinct union plane; a batch is then one index upload and one gather launch')
     args = ap.parse_args(argv)
+    if args.resident_gier and (args.dataset != 'GIER' or args.synthetic or args.device_resize or args.resident):
+        ap.error('--resident_gier keeps a GIER tree on the device: it needs --dataset GIER and takes none of --synthetic, '
+                 '--device_resize and --resident')
     if args.resident and (args.synthetic or args.dataset == 'GIER'):
         ap.error('--resident keeps a FiveK tree on the device: neither --synthetic nor --dataset GIER')
     if args.load_mask and args.dataset != 'GIER':
@@ -144,13 +153,14 @@ def main(argv=None):
     if gier_run:
         # train_GIER_seq2seqL1.py:157-164: GIERDatasetAct for training, GIERDataset('val') for validation, is_load_mask = False
         # (global edits only) unless --load_mask; the vocabularies are GIER's (options.dataset -> actor._vocab_sizes)
-        from .gier import GIERDataset, GIERDatasetAct, MaskTable, _Tuples, collate_masks
-        dataset = _Tuples(GIERDatasetAct(args.data_dir, args.vocab_dir, args.act_dir, 'train', args.data_mode,
-                                         'rle' if args.load_mask else False, args.session, args.img_size), with_masks=args.load_mask)
+        from .gier import GIERDataset, GIERDatasetAct, MaskTable, ResidentGIER, _Tuples, collate_masks
+        items = GIERDatasetAct(args.data_dir, args.vocab_dir, args.act_dir, 'train', args.data_mode,
+                               'rle' if args.load_mask else False, args.session, args.img_size)
+        dataset = _Tuples(items, with_masks=args.load_mask)
     else:
         dataset = SyntheticFiveK(n=args.batch_size * 64, size=args.img_size) if args.synthetic else \
             FiveKAct(args.img_dir, args.anno_dir, args.act_dir, 'train', 1, args.img_size, raw=raw or args.resident)
-    sampler = DistributedSampler(dataset, world, rank, shuffle=True) if world > 1 and not args.resident else None
+    sampler = DistributedSampler(dataset, world, rank, shuffle=True) if world > 1 and not (args.resident or args.resident_gier) else None
     raw_kw = dict(collate_fn=collate_raw, pin_memory=True) if raw else {}
     loader = DataLoader(dataset, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler,
                         num_workers=args.num_workers, drop_last=True, **(dict(collate_fn=collate_masks) if args.load_mask else raw_kw))
@@ -160,6 +170,12 @@ def main(argv=None):
         if rank == 0:
             print('resident set: {} items, {} bytes on the device, built in {:.1f} s'.format(
                 len(dataset), loader.nbytes, loader.build_seconds), flush=True)
+    if args.resident_gier:                                           # the same for GIER items: distinct pictures and planes once
+        loader = ResidentGIER(items, args.img_size, args.batch_size, device, seed=args.manual_seed, rank=rank, world=world,
+                              num_workers=args.num_workers, n_vocab=model.decoder.output_size)
+        if rank == 0:
+            print('resident GIER set: {} items, {} distinct pictures, {} mask planes, {} bytes on the device, built in {:.1f} s'.format(
+                len(items), loader.n_pictures, loader.n_planes, loader.nbytes, loader.build_seconds), flush=True)
     if gier_run:
         val_loader = DataLoader(_Tuples(GIERDataset(args.data_dir, args.vocab_dir, 'val', args.data_mode, False, args.session)),
                                 batch_size=1, shuffle=False, num_workers=1)
@@ -187,7 +203,9 @@ def main(argv=None):
             if raw and not args.resident:                            # decoded bytes: one upload, one resize launch
                 batch = device_batch(batch, args.img_size, device, images_only=True)
             masks = None
-            if args.load_mask:                                       # the batch's union planes: one upload, one launch
+            if args.load_mask and args.resident_gier:                # the resident planes, the batch's rows: nothing to upload
+                batch, masks = batch[:-1], batch[-1]
+            elif args.load_mask:                                     # the batch's union planes: one upload, one launch
                 batch, rles = batch[:-1], batch[-1]
                 masks = MaskTable.from_rle(rles, (args.img_size, args.img_size), model.decoder.output_size, device)
             img_x, img_y, x, y, gt_params, _ = batch
