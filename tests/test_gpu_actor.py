@@ -625,7 +625,8 @@ def test_graphed_training_stays_on_the_eager_trajectory():
 def test_graph_memset_nodes_become_kernel_nodes():
     """t2o_graph_memsets_to_kernels on a captured graph: kernel -> hipMemsetAsync (part of the buffer) -> kernel.  The
     rewritten graph has no memset node left, keeps the order (the fill runs between the two kernels) and the values
-    (1-, 2- and 4-byte patterns)."""
+    (1- and 4-byte patterns; 2-byte patterns, 2-D fills, memsets as first and last node and fills of more than one grid
+    pass: tests/test_gpu_step_graph_fill.py)."""
     import ctypes
     from t2onet_amd import graphs
     dev = torch.device('cuda:0')
