@@ -831,6 +831,31 @@ int t2o_replay_u8_masked(const unsigned char* src, unsigned char* out, const t2o
                          const float* params, const unsigned char* masks, const long long* mask_offsets, int n_masks,
                          void* stream);
 
+/* ---- the same replay for lists with ANY number of sharpness steps (t2o_replay_stencils.hip), masks optional: the
+ * arguments, limits (J <= 64 jobs, n_masks <= 4, steps <= 8) and per-step semantics of t2o_replay_u8_masked, and no limit
+ * on the sharpness steps among a list's 8.  Per job, with x = byte / 255, for k < steps:
+ *   x = clamp01(blend(process(ops[k], x, params[j][k]), x, m_k / 255))   where step k names a mask,
+ *   x = clamp01(process(ops[k], x, params[j][k]))                        where it names none;
+ * EVERY sharpness reads the four neighbours of the image in front of it, and that intermediate image counts as ZERO
+ * outside the picture (the intermediate image is padded, not the source; the zeros are not process(0)).  A masked
+ * sharpness blends with the stencil's input at the centre pixel.  byte = x * 255 truncated.  The bytes are those of the
+ * materialised path (resize at the picture's size, t2o_op_fwd per step, f32_to_u8_hwc): the same device functions in the
+ * same order.  A workgroup stages its 32 x 32 tile plus a ring of R pixels (R = the job's number of sharpness steps) and
+ * recomputes the per-pixel steps on the ring, up to (32 + 2R)^2 / 32^2 of the work; global traffic stays 6 bytes per
+ * pixel plus 1 per distinct mask named, plus the ring.  Lists with no or one sharpness are served too (same bytes as
+ * t2o_replay_u8 / t2o_replay_u8_masked, which are the cheaper kernels for them).  A step whose mask is 0 on a
+ * workgroup's whole window is skipped (same bytes).
+ * mask_of, masks and mask_offsets may be NULL when n_masks = 0.  jobs, mask_of, mask_offsets: HOST; params, masks:
+ * DEVICE.  One launch; no allocation, no host synchronisation, capturable, deterministic.  The caller guarantees that
+ * offsets and sizes lie inside src / out / masks.
+ * Status codes: operator 4 (inpaint) T2O_EUNSUPPORTED; everything else as t2o_replay_u8_masked; there is no status for
+ * "too many sharpness steps".  Adding this entry point does not change t2o_abi_version() (4): no existing form changed.
+ * Measured on one synthetic 4000 x 6000 picture only (profiles/replay_u8_stencils.txt); not measured: real photos
+ * through the decoder, more than two sharpness steps, the kernel's share of peak. */
+int t2o_replay_u8_stencils(const unsigned char* src, unsigned char* out, const t2o_replay_job_t* jobs, const int* mask_of, int J,
+                           const float* params, const unsigned char* masks, const long long* mask_offsets, int n_masks,
+                           void* stream);
+
 /* ---- feathering the mask planes of a local edit on the device (t2o_feather.hip): a hard 0/255 selection gets the soft
  * edge a photo wants.  Job j blurs the (h,w) uint8 plane at src + src_offset (any byte alignment) with a separable
  * Gaussian of standard deviation sigma (pixels of the plane, 0 <= sigma <= 64) in INTEGER arithmetic with replicated

@@ -163,6 +163,7 @@ SIGNATURES = {
     't2o_gather_items_u8_to_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
     't2o_replay_u8': (_I, [_P, _P, _P, _I, _P, _P]),
     't2o_replay_u8_masked': (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
+    't2o_replay_u8_stencils': (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
     't2o_feather_weights': (_I, [_D, _P, _P]),
     't2o_feather_workspace_bytes': (_Z, [_P, _I]),
     't2o_feather_u8': (_I, [_P, _P, _P, _I, _P, _Z, _P]),

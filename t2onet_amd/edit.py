@@ -8,7 +8,7 @@ import torch
 
 from . import functional as T
 from .actor import OP_MASK
-from .data import short_side_size, txt2idx
+from .data import ACTIONS, short_side_size, txt2idx
 
 
 def request_to_idx(text, vocab2id, opt):
@@ -112,7 +112,10 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None):
       params    (n, 24) fp32 GPU tensor, their parameter rows.
     The photo is uploaded once; the proxy is made on the device only when the short side exceeds proxy_short (no
     upscaling: a smaller photo is its own proxy); the arg-max episode runs in eval mode under no_grad; pred_ops is read
-    back once; ONE replay_u8 launch writes every prefix of the list at native size.
+    back once; ONE replay_u8 launch writes every prefix of the list at native size.  Nothing keeps the actor from
+    choosing the sharpness more than once: such a list goes, with or without masks, through ONE replay_u8_stencils launch
+    instead (every sharpness reads the neighbours of the image in front of it); lists with at most one sharpness keep
+    replay_u8 / replay_u8_masked, the cheaper kernels for them, and their bytes.
     masks: None (a global edit), or {executor operator index or 'all': uint8 (h, w) array at the photo's NATIVE size} for
     a local edit -- 0 leaves a pixel, 255 applies the operator, values between feather the edge; 'all' stands for every
     operator the actor can choose, an entry for one operator wins over it.  The planes travel behind the photo in the same
@@ -160,9 +163,13 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None):
     jobs = [(src_offset, j * nbytes, h, w, ops[:j + 1]) for j in range(J)]       # n = 0: one job with no step
     table = torch.zeros(J, T.REPLAY_MAX_STEPS, T.PARAM_PAD, device=dev)
     table[:, :n] = params
-    if masks is None:
+    mask_of = [by_op.get(op, -1) for op in ops]
+    if sum(op == ACTIONS.index('sharpness') for op in ops) >= 2:         # the two kernels below refuse a second sharpness
+        if masks is not None:
+            jobs = [job + (mask_of[:j + 1],) for j, job in enumerate(jobs)]
+        out = T.replay_u8_stencils(dev_buffer, jobs, table, dev_buffer if masks is not None else None, mask_offsets)
+    elif masks is None:
         out = T.replay_u8(dev_buffer, jobs, table)
     else:
-        mask_of = [by_op.get(op, -1) for op in ops]
         out = T.replay_u8_masked(dev_buffer, [job + (mask_of[:j + 1],) for j, job in enumerate(jobs)], table, dev_buffer, mask_offsets)
     return out[:J * nbytes].view(J, h, w, 3), ops, params

@@ -2135,6 +2135,39 @@ def replay_u8_masked(src_u8, jobs, params, masks_u8, mask_offsets, out=None):
     return out
 
 
+def replay_u8_stencils(src_u8, jobs, params, masks_u8=None, mask_offsets=(), out=None):
+    """replay_u8 / replay_u8_masked for lists with ANY number of sharpness steps, ONE launch (t2o_replay_u8_stencils):
+    jobs are 5-tuples (src_offset, out_offset, h, w, ops) as for replay_u8 or 6-tuples with mask_of as for
+    replay_u8_masked (a 5-tuple names no mask); masks_u8 / mask_offsets as there, None / () for a global edit.  Every
+    sharpness reads the four neighbours of the image in front of it, zero outside the picture; a masked one blends with
+    its input at the centre.  The bytes equal resize_u8 at the picture's size -> operator_apply(op, x, param[, mask]) per
+    step -> to_u8_hwc.  Lists with at most one sharpness give replay_u8's / replay_u8_masked's bytes, at a higher cost
+    (the window is recomputed on a ring of one pixel per sharpness).  Returns out (1-D uint8)."""
+    jobs, out, params = _replay_args('replay_u8_stencils', src_u8, jobs, params, out)
+    for j, job in enumerate(jobs):
+        if len(job) not in (5, 6):
+            raise ValueError('replay_u8_stencils: job %d has %d fields, 5 or 6 are taken' % (j, len(job)))
+    jobs = [job if len(job) == 6 else job + ([-1] * len(job[4]),) for job in jobs]
+    mask_offsets = [int(o) for o in mask_offsets]
+    if len(mask_offsets) > REPLAY_MAX_MASKS:
+        raise ValueError('replay_u8_stencils: at most 4 masks per launch, got %d' % len(mask_offsets))
+    if mask_offsets and not (torch.is_tensor(masks_u8) and masks_u8.is_cuda and masks_u8.dtype == torch.uint8
+                             and masks_u8.is_contiguous() and masks_u8.device == src_u8.device):
+        raise ValueError('replay_u8_stencils: masks must be a contiguous uint8 GPU tensor on the source\'s device')
+    for j, (_, _, h, w, ops, mask_of) in enumerate(jobs):
+        if len(mask_of) > len(ops):
+            raise ValueError('replay_u8_stencils: job %d names %d masks for %d steps' % (j, len(mask_of), len(ops)))
+        for i in mask_of if h > 0 and w > 0 else ():             # (an empty picture: the library refuses it)
+            if 0 <= i < len(mask_offsets) and not (0 <= mask_offsets[i] and mask_offsets[i] + h * w <= masks_u8.numel()):
+                raise ValueError('replay_u8_stencils: job %d reads mask %d outside the %d-byte mask buffer' % (j, i, masks_u8.numel()))
+    offs = (ctypes.c_longlong * max(len(mask_offsets), 1))(*mask_offsets)
+    rc = _lib.load().t2o_replay_u8_stencils(_ptr(src_u8), _ptr(out), replay_jobs([j[:5] for j in jobs]), replay_mask_table(jobs),
+                                            len(jobs), _ptr(params), _ptr(masks_u8) if mask_offsets else None, offs,
+                                            len(mask_offsets), _stream(src_u8.device))
+    replay_status(rc, 't2o_replay_u8_stencils')
+    return out
+
+
 # ---- local-edit masks (t2o_mask.hip): run-length masks resized and unioned on the device; the per-step mask select ----
 
 RLE_MASK = np.dtype([('first_end', '<u4'), ('n_runs', '<i4'), ('h', '<i4'), ('w', '<i4')])                    # t2o_rle_mask_t
