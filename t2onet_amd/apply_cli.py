@@ -10,7 +10,8 @@ the reference's operator names and parameter counts (data.ACTIONS / ACT2PN); an 
 
 The photos are decoded on the host, packed back to back and uploaded once; each photo is one job of the fused 8-bit
 replay at its native size (with --multi_img: one job per prefix of the list), at most 64 jobs per launch.  A list with at
-most one sharpness goes through functional.replay_u8, any other through functional.replay_u8_stencils.  The files of each
+most one sharpness goes through functional.replay_u8, any other through functional.replay_u8_stencils
+(functional.replay_u8_any chooses per launch).  The files of each
 photo are edit_cli's (write_outputs); the new record takes 'request' from the source record and names it under 'record'.
 Global edits only: masks stay with edit_cli --mask.
 """
@@ -24,7 +25,6 @@ import torch
 from .data import ACT2PN, ACTIONS, decode_image
 
 MAX_STEPS, MAX_JOBS, PARAM_PAD = 8, 64, 24          # functional.REPLAY_MAX_STEPS, REPLAY_MAX_JOBS, PARAM_PAD (checked in apply_record)
-SHARPNESS = ACTIONS.index('sharpness')
 
 
 def parse_record(record):
@@ -57,8 +57,9 @@ def parse_record(record):
 
 def pick_wrapper(ops):
     """The name of the functional wrapper that serves `ops`: replay_u8 keeps the lists it takes (it is the cheaper
-    kernel), replay_u8_stencils takes those that repeat the sharpness."""
-    return 'replay_u8' if sum(op == SHARPNESS for op in ops) <= 1 else 'replay_u8_stencils'
+    kernel), replay_u8_stencils takes those that repeat the sharpness.  The rule itself is functional.replay_u8_pick's."""
+    from . import functional as T
+    return T.replay_u8_pick([(0, 0, 0, 0, ops)])
 
 
 def job_lists(shapes, offsets, ops, multi_img=False):
@@ -89,14 +90,13 @@ def apply_record(images, ops, params, multi_img=False, device=None):
     buffer, descs = T.pack_u8(images)
     dev_buffer, _, descs, _keep = T.upload_packed(buffer, descs, device)
     shapes = [(int(d['h']), int(d['w'])) for d in descs]
-    wrapper = getattr(T, pick_wrapper(ops))
     row = torch.zeros(MAX_STEPS, PARAM_PAD)
     row[:len(ops)] = torch.as_tensor(np.asarray(params, np.float32).reshape(len(ops), PARAM_PAD))
     row = row.to(device)
     steps = [[] for _ in images]
     for launch in job_lists(shapes, [int(d['offset']) for d in descs], ops, multi_img):
         jobs = [job for _, job in launch]
-        out = wrapper(dev_buffer, jobs, row.unsqueeze(0).expand(len(jobs), -1, -1).contiguous()).cpu().numpy()
+        out = T.replay_u8_any(dev_buffer, jobs, row.unsqueeze(0).expand(len(jobs), -1, -1).contiguous()).cpu().numpy()
         for i, (_, pos, h, w, _) in launch:
             steps[i].append(out[pos:pos + 3 * h * w].reshape(h, w, 3))
     return [np.stack(s) for s in steps]

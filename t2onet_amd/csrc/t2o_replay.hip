@@ -7,10 +7,12 @@
 //                 sharpness list), moved as aligned dwords whatever the pictures' byte alignment; everything between the
 //                 two conversions lives in registers, with one LDS exchange for the stencil.  The job table travels in
 //                 the kernel arguments: no allocation, no host synchronisation, capturable, deterministic.
+// Host side, shared by the three replay entry points: replay_launch_prepare (t2o_replay_mask_math.h) checks the arguments
+// and fills the job table through replay_job_fill (t2o_replay_math.h); the entry point copies the jobs into the plain kernel's form.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
-#include "t2o_replay_math.h"
+#include "t2o_replay_mask_math.h"
 #include "t2onet_hip.h"
 
 namespace t2o { int set_error(int code, const char* msg); }
@@ -40,23 +42,17 @@ __global__ __launch_bounds__(kReplayThreads) void k_replay_u8(const ReplayArgs a
 
 extern "C" int t2o_replay_u8(const unsigned char* src, unsigned char* out, const t2o_replay_job_t* jobs, int J, const float* params,
                              void* stream) {
-  if (!src || !out || !jobs) return set_error(T2O_EINVAL, "replay_u8: null pointer");
-  if (J <= 0 || J > kReplayMaxJobs) return set_error(T2O_EINVAL, "replay_u8: 1 <= J <= 64 jobs per launch");
+  ReplayMaskArgs m;
+  const char* why = "";
+  unsigned tiles = 0;
+  int ring = 0;
+  if (const int rc = replay_launch_prepare(m, "replay_u8", kReplaySharpIndex, src, out, jobs, nullptr, J, params, nullptr, nullptr, 0,
+                                           &tiles, &ring, &why))
+    return set_error(rc, why);
   ReplayArgs a;
   memset(&a, 0, sizeof(a));
-  long long max_tiles = 0;
-  bool any_step = false;
-  for (int i = 0; i < J; ++i) {
-    const t2o_replay_job_t& s = jobs[i];
-    const char* why = "";
-    if (const int rc = replay_job_make(a.jobs[i], s.src_offset, s.out_offset, s.h, s.w, s.steps, s.ops, &why)) return set_error(rc, why);
-    for (int k = 0; k < s.steps; ++k) any_step = any_step || s.ops[k] >= 0;
-    const long long tiles = (long long)((s.w + kReplayTile - 1) / kReplayTile) * ((s.h + kReplayTile - 1) / kReplayTile);
-    max_tiles = tiles > max_tiles ? tiles : max_tiles;
-  }
-  if (any_step && !params) return set_error(T2O_EINVAL, "replay_u8: null parameter table");
-  if (max_tiles > 0x7fffffffll) return set_error(T2O_EINVAL, "replay_u8: more than 2^31 - 1 tiles in a picture");
   a.src = src; a.out = out; a.params = params;
-  k_replay_u8<<<dim3((unsigned)max_tiles, (unsigned)J), kReplayThreads, 0, (hipStream_t)stream>>>(a);
+  for (int i = 0; i < J; ++i) a.jobs[i] = m.jobs[i].j;               // no step names a mask: the plain kernel's job form
+  k_replay_u8<<<dim3(tiles, (unsigned)J), kReplayThreads, 0, (hipStream_t)stream>>>(a);
   return hipGetLastError() == hipSuccess ? T2O_OK : set_error(T2O_ELAUNCH, "replay_u8 launch failed");
 }

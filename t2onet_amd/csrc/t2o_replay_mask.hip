@@ -9,8 +9,9 @@
 //                        step whose mask is zero over the workgroup's window is skipped (same bytes, see the header).
 //                        The job table, the mask offsets and the per-step mask indices travel in the kernel arguments:
 //                        no allocation, no host synchronisation, capturable, deterministic.
+// Host side, shared by the three replay entry points: replay_launch_prepare (t2o_replay_mask_math.h) checks the arguments
+// and fills the job table through replay_job_fill (t2o_replay_math.h).
 #include <hip/hip_runtime.h>
-#include <string.h>
 
 #include "t2o_replay_mask_math.h"
 #include "t2onet_hip.h"
@@ -49,31 +50,14 @@ __global__ __launch_bounds__(kReplayThreads) void k_replay_u8_masked(const Repla
 extern "C" int t2o_replay_u8_masked(const unsigned char* src, unsigned char* out, const t2o_replay_job_t* jobs, const int* mask_of,
                                     int J, const float* params, const unsigned char* masks, const long long* mask_offsets,
                                     int n_masks, void* stream) {
-  if (!src || !out || !jobs || !mask_of) return set_error(T2O_EINVAL, "replay_u8_masked: null pointer");
-  if (J <= 0 || J > kReplayMaxJobs) return set_error(T2O_EINVAL, "replay_u8_masked: 1 <= J <= 64 jobs per launch");
-  if (n_masks < 0 || n_masks > kReplayMaxMasks) return set_error(T2O_EINVAL, "replay_u8_masked: at most 4 masks per launch");
-  if (n_masks > 0 && (!masks || !mask_offsets)) return set_error(T2O_EINVAL, "replay_u8_masked: null mask buffer or offset table");
+  if (!mask_of) return set_error(T2O_EINVAL, "replay_u8_masked: null pointer");      // its own: required even without masks
   ReplayMaskArgs a;
-  memset(&a, 0, sizeof(a));
-  for (int i = 0; i < n_masks; ++i) {
-    if (mask_offsets[i] < 0) return set_error(T2O_EINVAL, "replay_u8_masked: negative mask offset");
-    a.mask_offsets[i] = mask_offsets[i];
-  }
-  long long max_tiles = 0;
-  bool any_step = false;
-  for (int i = 0; i < J; ++i) {
-    const t2o_replay_job_t& s = jobs[i];
-    const char* why = "";
-    if (const int rc = replay_mask_job_make(a.jobs[i], s.src_offset, s.out_offset, s.h, s.w, s.steps, s.ops,
-                                            mask_of + (size_t)i * kReplayMaxSteps, n_masks, &why))
-      return set_error(rc, why);
-    for (int k = 0; k < s.steps; ++k) any_step = any_step || s.ops[k] >= 0;
-    const long long tiles = (long long)((s.w + kReplayTile - 1) / kReplayTile) * ((s.h + kReplayTile - 1) / kReplayTile);
-    max_tiles = tiles > max_tiles ? tiles : max_tiles;
-  }
-  if (any_step && !params) return set_error(T2O_EINVAL, "replay_u8_masked: null parameter table");
-  if (max_tiles > 0x7fffffffll) return set_error(T2O_EINVAL, "replay_u8_masked: more than 2^31 - 1 tiles in a picture");
-  a.src = src; a.out = out; a.params = params; a.masks = masks;
-  k_replay_u8_masked<<<dim3((unsigned)max_tiles, (unsigned)J), kReplayThreads, 0, (hipStream_t)stream>>>(a);
+  const char* why = "";
+  unsigned tiles = 0;
+  int ring = 0;
+  if (const int rc = replay_launch_prepare(a, "replay_u8_masked", kReplaySharpIndex, src, out, jobs, mask_of, J, params, masks,
+                                           mask_offsets, n_masks, &tiles, &ring, &why))
+    return set_error(rc, why);
+  k_replay_u8_masked<<<dim3(tiles, (unsigned)J), kReplayThreads, 0, (hipStream_t)stream>>>(a);
   return hipGetLastError() == hipSuccess ? T2O_OK : set_error(T2O_ELAUNCH, "replay_u8_masked launch failed");
 }

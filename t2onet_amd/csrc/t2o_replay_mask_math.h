@@ -45,18 +45,10 @@ T2O_HD unsigned replay_masks_used(const ReplayMaskJob& m) {
   return used;
 }
 
-// Host side: the job check of replay_job_make plus the per-step mask indices (mask_of: 8 ints, -1 = none; only the first
-// `steps` are looked at).  Same status codes.
+// Host side: the job check, replay_job_fill of t2o_replay_math.h, under the name this kernel's host emulation calls
 static inline int replay_mask_job_make(ReplayMaskJob& d, long long src_offset, long long out_offset, int h, int w, int steps,
                                        const int* ops, const int* mask_of, int n_masks, const char** why) {
-  if (const int rc = replay_job_make(d.j, src_offset, out_offset, h, w, steps, ops, why)) return rc;
-  d.mask_of = ~0ull;
-  for (int k = 0; k < steps; ++k) {
-    const int i = mask_of[k];
-    if (i < -1 || i >= n_masks) { *why = "replay_u8_masked: a step's mask index lies outside the mask table"; return 1; }
-    d.mask_of = (d.mask_of & ~(0xffull << (8 * k))) | ((unsigned long long)(unsigned char)(signed char)i << (8 * k));
-  }
-  return 0;
+  return replay_job_fill(d.j, d.mask_of, "replay_u8_masked", kReplaySharpIndex, src_offset, out_offset, h, w, steps, ops, mask_of, n_masks, why);
 }
 
 struct ReplayMaskArgs {
@@ -67,6 +59,44 @@ struct ReplayMaskArgs {
   long long mask_offsets[kReplayMaxMasks];     // first byte of mask i, counted from masks
   ReplayMaskJob jobs[kReplayMaxJobs];
 };
+
+// Host side: what the three entry points do alike in front of their launch: the checks in their order and `a` filled in.
+// AbiJob = t2o_replay_job_t; mask_of: (J, 8) or NULL; *grid_x, *max_ring = the largest tile count and ReplayJob::sharp.
+template <class AbiJob>
+static inline int replay_launch_prepare(ReplayMaskArgs& a, const char* who, ReplaySharp mode, const unsigned char* src,
+                                        unsigned char* out, const AbiJob* jobs, const int* mask_of, int J, const float* params,
+                                        const unsigned char* masks, const long long* mask_offsets, int n_masks,
+                                        unsigned* grid_x, int* max_ring, const char** why) {
+  if (!src || !out || !jobs) return replay_refuse(why, 1, who, "null pointer");
+  if (J <= 0 || J > kReplayMaxJobs) return replay_refuse(why, 1, who, "1 <= J <= 64 jobs per launch");
+  if (n_masks < 0 || n_masks > kReplayMaxMasks) return replay_refuse(why, 1, who, "at most 4 masks per launch");
+  if (n_masks > 0 && (!masks || !mask_offsets || !mask_of))
+    return replay_refuse(why, 1, who, mode == kReplaySharpIndex ? "null mask buffer or offset table"
+                                                                : "null mask buffer, offset table or mask index table");
+  memset(&a, 0, sizeof(a));
+  for (int i = 0; i < n_masks; ++i) {
+    if (mask_offsets[i] < 0) return replay_refuse(why, 1, who, "negative mask offset");
+    a.mask_offsets[i] = mask_offsets[i];
+  }
+  long long max_tiles = 0;
+  bool any_step = false;
+  *max_ring = 0;
+  for (int i = 0; i < J; ++i) {
+    const AbiJob& s = jobs[i];
+    if (const int rc = replay_job_fill(a.jobs[i].j, a.jobs[i].mask_of, who, mode, s.src_offset, s.out_offset, s.h, s.w, s.steps, s.ops,
+                                       mask_of ? mask_of + (size_t)i * kReplayMaxSteps : nullptr, n_masks, why))
+      return rc;
+    for (int k = 0; k < s.steps; ++k) any_step = any_step || s.ops[k] >= 0;
+    const long long tiles = (long long)((s.w + kReplayTile - 1) / kReplayTile) * ((s.h + kReplayTile - 1) / kReplayTile);
+    max_tiles = tiles > max_tiles ? tiles : max_tiles;
+    *max_ring = a.jobs[i].j.sharp > *max_ring ? a.jobs[i].j.sharp : *max_ring;
+  }
+  if (any_step && !params) return replay_refuse(why, 1, who, "null parameter table");
+  if (max_tiles > 0x7fffffffll) return replay_refuse(why, 1, who, "more than 2^31 - 1 tiles in a picture");
+  a.src = src; a.out = out; a.params = params; a.masks = masks;
+  *grid_x = (unsigned)max_tiles;
+  return 0;
+}
 
 struct ReplayMaskLds {
   ReplayLds base;

@@ -22,6 +22,7 @@
 #pragma once
 #ifndef __HIPCC_RTC__
 #include <stddef.h>
+#include <stdio.h>
 #include <string.h>
 #endif
 
@@ -51,27 +52,55 @@ struct ReplayJob {
 
 T2O_HD int replay_op(const ReplayJob& j, int k) { return (int)(signed char)(unsigned char)(j.ops >> (8 * k)); }
 
-// Host side: check one job of the C ABI and bring it into the kernel's form.  Returns 0, 1 (invalid argument) or 2
-// (unsupported: T2O_EINVAL / T2O_EUNSUPPORTED of t2onet_hip.h) with the reason in *why.
-static inline int replay_job_make(ReplayJob& d, long long src_offset, long long out_offset, int h, int w, int steps,
-                                  const int* ops, const char** why) {
-  if (h <= 0 || w <= 0) { *why = "replay_u8: h and w must be positive"; return 1; }
-  if (src_offset < 0 || out_offset < 0) { *why = "replay_u8: negative offset"; return 1; }
-  if (steps < 0 || steps > kReplayMaxSteps) { *why = "replay_u8: 0 <= steps <= 8"; return 1; }
+// ---- host side: ONE job check for t2o_replay_u8, t2o_replay_u8_masked and t2o_replay_u8_stencils.  A refusal leaves
+// "<entry point>: reason" in *why: a thread's buffer, good until its next refusal (t2o::set_error copies it). ----
+static inline int replay_refuse(const char** why, int rc, const char* who, const char* reason) {
+  static thread_local char text[160];
+  snprintf(text, sizeof(text), "%s: %s", who, reason);
+  *why = text;
+  return rc;
+}
+
+// ReplayJob::sharp holds the index of the sharpness step (-1 = none) and a second one is refused, or their number R
+enum ReplaySharp { kReplaySharpIndex, kReplaySharpCount };
+
+// Check one job of the C ABI and bring it into the kernel's form: d, and mask_bits = ReplayMaskJob::mask_of (step k's mask
+// index as a signed byte at bits [8k, 8k+8)).  mask_of: 8 ints, NULL = none.  Returns 0, 1 (T2O_EINVAL) or 2 (T2O_EUNSUPPORTED).
+// Kept as they were: the kReplaySharpIndex entry points call a job's refusals "replay_u8" and look at every operator first.
+static inline int replay_job_fill(ReplayJob& d, unsigned long long& mask_bits, const char* who, ReplaySharp mode, long long src_offset,
+                                  long long out_offset, int h, int w, int steps, const int* ops, const int* mask_of, int n_masks,
+                                  const char** why) {
+  const char* job_who = mode == kReplaySharpIndex ? "replay_u8" : who;
+  if (h <= 0 || w <= 0) return replay_refuse(why, 1, job_who, "h and w must be positive");
+  if (src_offset < 0 || out_offset < 0) return replay_refuse(why, 1, job_who, "negative offset");
+  if (steps < 0 || steps > kReplayMaxSteps) return replay_refuse(why, 1, job_who, "0 <= steps <= 8");
   d.src_offset = src_offset; d.out_offset = out_offset;
-  d.h = h; d.w = w; d.steps = steps; d.sharp = -1;
-  d.ops = ~0ull;                                   // every step the identity (-1) until set
+  d.h = h; d.w = w; d.steps = steps; d.sharp = mode == kReplaySharpIndex ? -1 : 0;
+  d.ops = mask_bits = ~0ull;                       // every step the identity (-1) and without a mask until set
+  bool bad_mask = false;
   for (int k = 0; k < steps; ++k) {
     const int op = ops[k];
-    if (op == OP_INPAINT) { *why = "replay_u8: operator 4 (inpaint) is not supported"; return 2; }
-    if (op < OP_IDENTITY || op > OP_WHITE) { *why = "replay_u8: operator index outside -1, 0..7"; return 1; }
+    if (op == OP_INPAINT) return replay_refuse(why, 2, job_who, "operator 4 (inpaint) is not supported");
+    if (op < OP_IDENTITY || op > OP_WHITE) return replay_refuse(why, 1, job_who, "operator index outside -1, 0..7");
     if (op == OP_SHARPNESS) {
-      if (d.sharp >= 0) { *why = "replay_u8: more than one sharpness in a job's list (the 1-pixel halo serves one)"; return 2; }
-      d.sharp = k;
+      if (mode == kReplaySharpCount) ++d.sharp;
+      else if (d.sharp >= 0) return replay_refuse(why, 2, job_who, "more than one sharpness in a job's list (the 1-pixel halo serves one)");
+      else d.sharp = k;
     }
     d.ops = (d.ops & ~(0xffull << (8 * k))) | ((unsigned long long)(unsigned char)(signed char)op << (8 * k));
+    const int i = mask_of ? mask_of[k] : -1;
+    bad_mask = bad_mask || i < -1 || i >= n_masks;
+    if (bad_mask && mode == kReplaySharpCount) break;      // (kReplaySharpIndex: reported behind the later steps' operators)
+    mask_bits = (mask_bits & ~(0xffull << (8 * k))) | ((unsigned long long)(unsigned char)(signed char)i << (8 * k));
   }
-  return 0;
+  return bad_mask ? replay_refuse(why, 1, who, "a step's mask index lies outside the mask table") : 0;
+}
+
+// (the name the plain kernel's host emulation calls it by)
+static inline int replay_job_make(ReplayJob& d, long long src_offset, long long out_offset, int h, int w, int steps,
+                                  const int* ops, const char** why) {
+  unsigned long long none;
+  return replay_job_fill(d, none, "replay_u8", kReplaySharpIndex, src_offset, out_offset, h, w, steps, ops, nullptr, 0, why);
 }
 
 struct ReplayArgs {

@@ -30,8 +30,9 @@
 // Measured on one synthetic 4000 x 6000 picture (profiles/replay_u8_stencils.txt, medians of 20): [0,6,1,6,5] 0.537 ms
 // against 0.771 ms of the materialised path (0.70 of it); [0,6,1,2,5] 0.442 ms against 0.312 ms of t2o_replay_u8 (1.42x).
 // Not measured: real photos through the decoder, R > 2 (the large instance), the kernel's share of peak.
+// Host side, shared by the three replay entry points: replay_launch_prepare (t2o_replay_mask_math.h) checks the arguments
+// and fills the job table through replay_job_fill (t2o_replay_math.h) (here in the mode that counts the sharpness steps).
 #include <hip/hip_runtime.h>
-#include <string.h>
 
 #include "t2o_replay_stencils_math.h"
 #include "t2onet_hip.h"
@@ -119,35 +120,14 @@ __global__ __launch_bounds__(kReplayThreads) void k_replay_u8_stencils(const Rep
 extern "C" int t2o_replay_u8_stencils(const unsigned char* src, unsigned char* out, const t2o_replay_job_t* jobs, const int* mask_of,
                                       int J, const float* params, const unsigned char* masks, const long long* mask_offsets,
                                       int n_masks, void* stream) {
-  if (!src || !out || !jobs) return set_error(T2O_EINVAL, "replay_u8_stencils: null pointer");
-  if (J <= 0 || J > kReplayMaxJobs) return set_error(T2O_EINVAL, "replay_u8_stencils: 1 <= J <= 64 jobs per launch");
-  if (n_masks < 0 || n_masks > kReplayMaxMasks) return set_error(T2O_EINVAL, "replay_u8_stencils: at most 4 masks per launch");
-  if (n_masks > 0 && (!masks || !mask_offsets || !mask_of))
-    return set_error(T2O_EINVAL, "replay_u8_stencils: null mask buffer, offset table or mask index table");
   ReplayMaskArgs a;
-  memset(&a, 0, sizeof(a));
-  for (int i = 0; i < n_masks; ++i) {
-    if (mask_offsets[i] < 0) return set_error(T2O_EINVAL, "replay_u8_stencils: negative mask offset");
-    a.mask_offsets[i] = mask_offsets[i];
-  }
-  long long max_tiles = 0;
+  const char* why = "";
+  unsigned tiles = 0;
   int max_ring = 0;
-  bool any_step = false;
-  for (int i = 0; i < J; ++i) {
-    const t2o_replay_job_t& s = jobs[i];
-    const char* why = "";
-    if (const int rc = replay_st_job_make(a.jobs[i], s.src_offset, s.out_offset, s.h, s.w, s.steps, s.ops,
-                                          mask_of ? mask_of + (size_t)i * kReplayMaxSteps : nullptr, n_masks, &why))
-      return set_error(rc, why);
-    for (int k = 0; k < s.steps; ++k) any_step = any_step || s.ops[k] >= 0;
-    const long long tiles = (long long)((s.w + kReplayTile - 1) / kReplayTile) * ((s.h + kReplayTile - 1) / kReplayTile);
-    max_tiles = tiles > max_tiles ? tiles : max_tiles;
-    max_ring = a.jobs[i].j.sharp > max_ring ? a.jobs[i].j.sharp : max_ring;
-  }
-  if (any_step && !params) return set_error(T2O_EINVAL, "replay_u8_stencils: null parameter table");
-  if (max_tiles > 0x7fffffffll) return set_error(T2O_EINVAL, "replay_u8_stencils: more than 2^31 - 1 tiles in a picture");
-  a.src = src; a.out = out; a.params = params; a.masks = masks;
-  const dim3 grid((unsigned)max_tiles, (unsigned)J);
+  if (const int rc = replay_launch_prepare(a, "replay_u8_stencils", kReplaySharpCount, src, out, jobs, mask_of, J, params, masks,
+                                           mask_offsets, n_masks, &tiles, &max_ring, &why))
+    return set_error(rc, why);
+  const dim3 grid(tiles, (unsigned)J);
   if (max_ring <= kStSmallRing) k_replay_u8_stencils<kStSmallRing><<<grid, kReplayThreads, 0, (hipStream_t)stream>>>(a);
   else k_replay_u8_stencils<kStMaxRing><<<grid, kReplayThreads, 0, (hipStream_t)stream>>>(a);
   return hipGetLastError() == hipSuccess ? T2O_OK : set_error(T2O_ELAUNCH, "replay_u8_stencils launch failed");

@@ -75,28 +75,10 @@ T2O_HD int replay_st_next_sharp(const ReplayJob& j, int k) {
   return k;
 }
 
-// Host side: replay_mask_job_make's checks and status codes without the refusal of a second sharpness; d.j.sharp = R.
-// mask_of may be NULL when n_masks = 0 (no step names a mask).
+// Host side: replay_job_fill counting the sharpness steps, d.j.sharp = R (the host emulation's name); mask_of may be NULL
 static inline int replay_st_job_make(ReplayMaskJob& d, long long src_offset, long long out_offset, int h, int w, int steps,
                                      const int* ops, const int* mask_of, int n_masks, const char** why) {
-  if (h <= 0 || w <= 0) { *why = "replay_u8_stencils: h and w must be positive"; return 1; }
-  if (src_offset < 0 || out_offset < 0) { *why = "replay_u8_stencils: negative offset"; return 1; }
-  if (steps < 0 || steps > kReplayMaxSteps) { *why = "replay_u8_stencils: 0 <= steps <= 8"; return 1; }
-  d.j.src_offset = src_offset; d.j.out_offset = out_offset;
-  d.j.h = h; d.j.w = w; d.j.steps = steps; d.j.sharp = 0;
-  d.j.ops = ~0ull;
-  d.mask_of = ~0ull;
-  for (int k = 0; k < steps; ++k) {
-    const int op = ops[k];
-    if (op == OP_INPAINT) { *why = "replay_u8_stencils: operator 4 (inpaint) is not supported"; return 2; }
-    if (op < OP_IDENTITY || op > OP_WHITE) { *why = "replay_u8_stencils: operator index outside -1, 0..7"; return 1; }
-    if (op == OP_SHARPNESS) ++d.j.sharp;
-    d.j.ops = (d.j.ops & ~(0xffull << (8 * k))) | ((unsigned long long)(unsigned char)(signed char)op << (8 * k));
-    const int i = mask_of ? mask_of[k] : -1;
-    if (i < -1 || i >= n_masks) { *why = "replay_u8_stencils: a step's mask index lies outside the mask table"; return 1; }
-    d.mask_of = (d.mask_of & ~(0xffull << (8 * k))) | ((unsigned long long)(unsigned char)(signed char)i << (8 * k));
-  }
-  return 0;
+  return replay_job_fill(d.j, d.mask_of, "replay_u8_stencils", kReplaySharpCount, src_offset, out_offset, h, w, steps, ops, mask_of, n_masks, why);
 }
 
 // the tile's origin and the part of the window (tile + R) that lies inside the picture

@@ -7,6 +7,8 @@
 //                     12 written per pixel, nothing else: the kernel is bound by the stores.
 // No atomics, no allocation, no host synchronisation; deterministic (every output element has one writer) and
 // capturable: a captured launch serves a new batch once the index buffer has been overwritten.
+// Host side: gather_check of t2o_resident_math.h checks the arguments and fills GatherArgs, here and (through items_check)
+// for t2o_resident_items.hip.
 #include <hip/hip_runtime.h>
 
 #include "t2o_resident_math.h"
@@ -27,12 +29,10 @@ __global__ __launch_bounds__(kGatherThreads) void k_gather_u8_f32(const GatherAr
 
 extern "C" int t2o_gather_u8_to_f32(const unsigned char* store, const long long* slot_offsets, const long long* index, int N, int K,
                                     int B, int h, int w, float* out_x, float* out_ys, void* stream) {
+  GatherArgs a;
   long long per_image = 0;
   const char* why = "";
-  if (gather_check(store, slot_offsets, index, N, K, B, h, w, out_x, out_ys, &per_image, &why)) return set_error(T2O_EINVAL, why);
-  GatherArgs a;
-  a.store = store; a.slots = slot_offsets; a.index = index; a.out_x = out_x; a.out_ys = out_ys;
-  a.hw = (long long)h * w; a.blocks_per_image = (unsigned)per_image; a.N = N; a.K = K; a.B = B;
+  if (gather_check(store, slot_offsets, index, N, K, B, h, w, out_x, out_ys, &per_image, &why, &a)) return set_error(T2O_EINVAL, why);
   k_gather_u8_f32<<<(unsigned)(per_image * K * B), kGatherThreads, 0, (hipStream_t)stream>>>(a);
   return hipGetLastError() == hipSuccess ? T2O_OK : set_error(T2O_ELAUNCH, "gather_u8_to_f32 launch failed");
 }

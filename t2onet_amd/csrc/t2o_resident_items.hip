@@ -8,6 +8,7 @@
 //                           is uniform over a workgroup.
 // No atomics, no allocation, no host synchronisation; deterministic (every output element has one writer) and
 // capturable: a captured launch serves a new batch, rows included, once the index buffer has been overwritten.
+// Host side: items_check checks the row table and leaves the pictures to gather_check (t2o_resident_math.h), as t2o_resident.hip.
 #include <hip/hip_runtime.h>
 
 #include "t2o_resident_items_math.h"

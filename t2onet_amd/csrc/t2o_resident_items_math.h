@@ -48,27 +48,18 @@ T2O_IMG_HD void items_thread(const ItemsArgs& a, unsigned block, unsigned thread
   gather_thread(a.g, (int)b, (int)(image - b * (unsigned)a.g.K), (long long)within * kGatherThreads + thread);
 }
 
-// ---- host-side checks of a launch (before any launch; no device value is read).  0 with *a filled in, or 1 with *why. ----
+// ---- host-side checks of a launch (before any launch; no device value is read): the row table's own, then gather_check of
+// t2o_resident_math.h for the pictures, with the row workgroups in its grid bound.  0 with *a filled in, or 1 with `why`. ----
 inline int items_check(const unsigned char* store, const long long* slots, const long long* index, int N, int K, int B, int h, int w,
                        float* out_x, float* out_ys, const int* rows, int V, int* out_rows, ItemsArgs* a, const char** why) {
-  if (!store || !slots || !index || !out_x || (K > 1 && !out_ys)) { *why = "gather_items_u8_to_f32: null pointer"; return 1; }
-  if (N <= 0 || K <= 0 || B <= 0 || h <= 0 || w <= 0) { *why = "gather_items_u8_to_f32: N, K, B, h and w must be positive"; return 1; }
-  if (K > kItemsMaxK) { *why = "gather_items_u8_to_f32: at most 16 pictures per item"; return 1; }
-  if (V < 0) { *why = "gather_items_u8_to_f32: V must not be negative"; return 1; }
-  if ((V > 0) != (rows != nullptr) || (V > 0) != (out_rows != nullptr)) {
-    *why = "gather_items_u8_to_f32: rows, out_rows and V do not agree (all three, or none with V = 0)";
-    return 1;
-  }
-  if (((size_t)store & 15) || ((size_t)slots & 7) || ((size_t)index & 7) || ((size_t)out_x & 3) || ((size_t)out_ys & 3) ||
-      ((size_t)rows & 3) || ((size_t)out_rows & 3)) {
-    *why = "gather_items_u8_to_f32: store 16-byte, slots and index 8-byte, outputs and rows 4-byte aligned";
-    return 1;
-  }
-  const long long per_image = (gather_groups((long long)h * w) + kGatherThreads - 1) / kGatherThreads;
+  const char *who = "gather_items_u8_to_f32", *aligned = "store 16-byte, slots and index 8-byte, outputs and rows 4-byte aligned";
+  if (V < 0) return gather_refuse(why, who, "V must not be negative");
+  if ((V > 0) != (rows != nullptr) || (V > 0) != (out_rows != nullptr))
+    return gather_refuse(why, who, "rows, out_rows and V do not agree (all three, or none with V = 0)");
+  if (((size_t)rows & 3) || ((size_t)out_rows & 3)) return gather_refuse(why, who, aligned);
   const long long row_blocks = ((long long)B * V + kGatherThreads - 1) / kGatherThreads;
-  if (per_image > (0x7fffffffll - row_blocks) / ((long long)K * B)) { *why = "gather_items_u8_to_f32: more than 2^31 - 1 workgroups"; return 1; }
-  a->g.store = store; a->g.slots = slots; a->g.index = index; a->g.out_x = out_x; a->g.out_ys = out_ys;
-  a->g.hw = (long long)h * w; a->g.blocks_per_image = (unsigned)per_image; a->g.N = N; a->g.K = K; a->g.B = B;
+  long long per_image = 0;
+  if (gather_check(store, slots, index, N, K, B, h, w, out_x, out_ys, &per_image, why, &a->g, who, kItemsMaxK, aligned, row_blocks)) return 1;
   a->rows = rows; a->out_rows = out_rows; a->V = V;
   a->picture_blocks = (unsigned)(per_image * K * B); a->row_blocks = (unsigned)row_blocks;
   return 0;

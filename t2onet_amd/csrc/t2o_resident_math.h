@@ -16,6 +16,7 @@
 // by thread (a test harness, never a fallback).
 #pragma once
 #include <stddef.h>
+#include <stdio.h>
 
 #include "t2o_image_math.h"
 
@@ -94,19 +95,36 @@ T2O_IMG_HD void gather_thread(const GatherArgs& a, int b, int k, long long t) {
   }
 }
 
-// ---- host-side checks of a launch (before any launch; no device value is read).  0, or 1 with *why set. ----
-inline int gather_check(const void* store, const void* slots, const void* index, int N, int K, int B, int h, int w,
-                        const void* out_x, const void* out_ys, long long* blocks, const char** why) {
-  if (!store || !slots || !index || !out_x || (K > 1 && !out_ys)) { *why = "gather_u8_to_f32: null pointer"; return 1; }
-  if (N <= 0 || K <= 0 || B <= 0 || h <= 0 || w <= 0) { *why = "gather_u8_to_f32: N, K, B, h and w must be positive"; return 1; }
-  if (K > kGatherMaxK) { *why = "gather_u8_to_f32: at most 8 pictures per item"; return 1; }
-  if (((size_t)store & 15) || ((size_t)slots & 7) || ((size_t)index & 7) || ((size_t)out_x & 3) || ((size_t)out_ys & 3)) {
-    *why = "gather_u8_to_f32: store 16-byte, tables 8-byte, outputs 4-byte aligned";
-    return 1;
-  }
+// ---- host-side checks of a launch (before any launch; no device value is read), for t2o_gather_u8_to_f32 and, through
+// items_check of t2o_resident_items_math.h, t2o_gather_items_u8_to_f32.  A refusal leaves "<entry point>: reason" in *why:
+// a thread's buffer, good until its next refusal (t2o::set_error copies it).  `reason` may hold one %d, for n. ----
+inline int gather_refuse(const char** why, const char* who, const char* reason, int n = 0) {
+  static thread_local char text[160];
+  const int at = snprintf(text, sizeof(text), "%s: ", who);
+  snprintf(text + at, sizeof(text) - at, reason, n);
+  *why = text;
+  return 1;
+}
+
+// The parent form (what t2o_gather_u8_to_f32's host emulation calls): *blocks = the workgroups of one picture.  Behind it:
+// a, filled in when given; who, max_k, aligned: the entry point's name, the pictures per item it takes and its alignment rule
+// as its message states it; more_blocks: workgroups the caller appends behind the pictures' (they count in the grid bound).
+inline int gather_check(const void* store, const void* slots, const void* index, int N, int K, int B, int h, int w, const void* out_x,
+                        const void* out_ys, long long* blocks, const char** why, GatherArgs* a = nullptr,
+                        const char* who = "gather_u8_to_f32", int max_k = kGatherMaxK,
+                        const char* aligned = "store 16-byte, tables 8-byte, outputs 4-byte aligned", long long more_blocks = 0) {
+  if (!store || !slots || !index || !out_x || (K > 1 && !out_ys)) return gather_refuse(why, who, "null pointer");
+  if (N <= 0 || K <= 0 || B <= 0 || h <= 0 || w <= 0) return gather_refuse(why, who, "N, K, B, h and w must be positive");
+  if (K > max_k) return gather_refuse(why, who, "at most %d pictures per item", max_k);
+  if (((size_t)store & 15) || ((size_t)slots & 7) || ((size_t)index & 7) || ((size_t)out_x & 3) || ((size_t)out_ys & 3))
+    return gather_refuse(why, who, aligned);
   const long long per_image = (gather_groups((long long)h * w) + kGatherThreads - 1) / kGatherThreads;
-  if (per_image > 0x7fffffffll / ((long long)K * B)) { *why = "gather_u8_to_f32: more than 2^31 - 1 workgroups"; return 1; }
+  if (per_image > (0x7fffffffll - more_blocks) / ((long long)K * B)) return gather_refuse(why, who, "more than 2^31 - 1 workgroups");
   *blocks = per_image;
+  if (!a) return 0;
+  a->store = (const unsigned char*)store; a->slots = (const long long*)slots; a->index = (const long long*)index;
+  a->out_x = (float*)out_x; a->out_ys = (float*)out_ys;
+  a->hw = (long long)h * w; a->blocks_per_image = (unsigned)per_image; a->N = N; a->K = K; a->B = B;
   return 0;
 }
 

@@ -8,7 +8,7 @@ import torch
 
 from . import functional as T
 from .actor import OP_MASK
-from .data import ACTIONS, short_side_size, txt2idx
+from .data import short_side_size, txt2idx
 
 
 def request_to_idx(text, vocab2id, opt):
@@ -163,13 +163,8 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None):
     jobs = [(src_offset, j * nbytes, h, w, ops[:j + 1]) for j in range(J)]       # n = 0: one job with no step
     table = torch.zeros(J, T.REPLAY_MAX_STEPS, T.PARAM_PAD, device=dev)
     table[:, :n] = params
-    mask_of = [by_op.get(op, -1) for op in ops]
-    if sum(op == ACTIONS.index('sharpness') for op in ops) >= 2:         # the two kernels below refuse a second sharpness
-        if masks is not None:
-            jobs = [job + (mask_of[:j + 1],) for j, job in enumerate(jobs)]
-        out = T.replay_u8_stencils(dev_buffer, jobs, table, dev_buffer if masks is not None else None, mask_offsets)
-    elif masks is None:
-        out = T.replay_u8(dev_buffer, jobs, table)
-    else:
-        out = T.replay_u8_masked(dev_buffer, [job + (mask_of[:j + 1],) for j, job in enumerate(jobs)], table, dev_buffer, mask_offsets)
+    if masks is not None:
+        mask_of = [by_op.get(op, -1) for op in ops]
+        jobs = [job + (mask_of[:j + 1],) for j, job in enumerate(jobs)]
+    out = T.replay_u8_any(dev_buffer, jobs, table, dev_buffer if masks is not None else None, mask_offsets)   # the kernel by the list
     return out[:J * nbytes].view(J, h, w, 3), ops, params

@@ -1949,6 +1949,44 @@ def _need_gpu_as(t, dtype, what):
                            'implementation' % (what, dtype, getattr(t, 'dtype', type(t)), getattr(t, 'device', 'the host')))
 
 
+def _gather(who, max_k, items, store, slots, index, size, rows, out):
+    """The one implementation behind gather_u8 and gather_items_u8 (`who`; items: the entry point takes rows, and the
+    messages say so): the tensors, the size, K against max_k, one device, `out` allocated or held against the shapes, then
+    the launch of t2o_<who>_to_f32.  Returns (img_x, img_ys) or, with rows, (img_x, img_ys, out_rows)."""
+    _need_gpu_as(store, torch.uint8, 'store')
+    _need_gpu_as(slots, torch.int64, 'slots')
+    _need_gpu_as(index, torch.int64, 'index')
+    if rows is not None:
+        _need_gpu_as(rows, torch.int32, 'rows')
+    h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    if store.dim() != 1 or slots.dim() != 2 or index.dim() != 1 or index.numel() == 0 or h <= 0 or w <= 0:
+        raise ValueError('%s: store (bytes,), slots (N,K), index (B,) with B > 0, positive size' % who)
+    N, K = slots.shape
+    if not 1 <= K <= max_k or N == 0:
+        raise ValueError('%s: slots must be (N,K) with N > 0 and 1 <= K <= %d' % (who, max_k))
+    B, dev = index.numel(), store.device
+    if rows is not None and (rows.dim() != 2 or rows.shape[0] != N or rows.shape[1] == 0):
+        raise ValueError('%s: rows must be (N,V) with the N of slots and V > 0' % who)
+    V = 0 if rows is None else rows.shape[1]
+    if slots.device != dev or index.device != dev or (rows is not None and rows.device != dev):
+        raise ValueError('%s: store, slots%s must lie on one device' % (who, ', index and rows' if items else ' and index'))
+    shapes = [(B, 3, h, w), (B, K - 1, 3, h, w)] + ([(B, V)] if V else [])
+    dtypes = [torch.float32, torch.float32, torch.int32]
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+    else:
+        out = tuple(out)
+        if len(out) != len(shapes) or not all(torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == d and t.is_contiguous()
+                                              and tuple(t.shape) == s for t, s, d in zip(out, shapes, dtypes)):
+            raise ValueError('%s: out must be contiguous %s' % (who, 'GPU tensors of shapes %s (fp32, fp32, int32)' % (shapes,) if items
+                                                                 else 'fp32 tensors of shapes %s and %s' % tuple(shapes)))
+    entry = 't2o_%s_to_f32' % who
+    rc = getattr(_lib.load(), entry)(_ptr(store), _ptr(slots), _ptr(index), N, K, B, h, w, _ptr(out[0]), _ptr(out[1]) if K > 1 else None,
+                                     *((_ptr(rows), V, _ptr(out[2]) if V else None) if items else ()), _stream(dev))
+    _lib.check(rc, entry)
+    return out
+
+
 def gather_u8(store, slots, index, size, out=None):
     """The pictures of the items `index` names out of a resident store, as the loaders' fp32 tensors: (img_x (B,3,h,w),
     img_ys (B,K-1,3,h,w)), each picture .astype(float32).transpose(2,0,1) / 255, an absent one zeros.
@@ -1956,31 +1994,10 @@ def gather_u8(store, slots, index, size, out=None):
     multiple of 16 -- or -1; index: (B,) int64 GPU tensor, read on the device (values in [0, N): the caller's promise,
     nothing reads them back); size: int or (h, w), the pictures' size.  out: an (img_x, img_ys) pair to write into -- a
     captured launch keeps serving new batches through the same three tensors.  One launch on the current stream."""
-    _need_gpu_as(store, torch.uint8, 'store')
-    _need_gpu_as(slots, torch.int64, 'slots')
-    _need_gpu_as(index, torch.int64, 'index')
-    h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
-    if store.dim() != 1 or slots.dim() != 2 or index.dim() != 1 or index.numel() == 0 or h <= 0 or w <= 0:
-        raise ValueError('gather_u8: store (bytes,), slots (N,K), index (B,) with B > 0, positive size')
-    N, K = slots.shape
-    if not 1 <= K <= GATHER_MAX_K or N == 0:
-        raise ValueError('gather_u8: slots must be (N,K) with N > 0 and 1 <= K <= %d' % GATHER_MAX_K)
-    B, dev = index.numel(), store.device
-    if slots.device != dev or index.device != dev:
-        raise ValueError('gather_u8: store, slots and index must lie on one device')
-    if out is None:
-        img_x = torch.empty(B, 3, h, w, dtype=torch.float32, device=dev)
-        img_ys = torch.empty(B, K - 1, 3, h, w, dtype=torch.float32, device=dev)
-    else:
+    if out is not None:
         img_x, img_ys = out
         _need_gpu(img_x, img_ys)
-        if not (img_x.is_contiguous() and img_ys.is_contiguous() and img_x.device == dev and img_ys.device == dev
-                and tuple(img_x.shape) == (B, 3, h, w) and tuple(img_ys.shape) == (B, K - 1, 3, h, w)):
-            raise ValueError('gather_u8: out must be contiguous fp32 tensors of shapes %s and %s' % ((B, 3, h, w), (B, K - 1, 3, h, w)))
-    rc = _lib.load().t2o_gather_u8_to_f32(_ptr(store), _ptr(slots), _ptr(index), N, K, B, h, w, _ptr(img_x),
-                                          _ptr(img_ys) if K > 1 else None, _stream(dev))
-    _lib.check(rc, 't2o_gather_u8_to_f32')
-    return img_x, img_ys
+    return _gather('gather_u8', GATHER_MAX_K, False, store, slots, index, size, None, out)
 
 
 GATHER_ITEMS_MAX_K = 16
@@ -1991,37 +2008,7 @@ def gather_items_u8(store, slots, index, size, rows=None, out=None):
     K <= 8 the same bits as gather_u8), and with `rows` -- an (N,V) int32 GPU table -- also out_rows (B,V) int32 =
     rows[index], written by the SAME launch (an index outside [0, N) gives a row of -1).  Returns (img_x, img_ys) or
     (img_x, img_ys, out_rows).  out: the tensors to write into, a pair or, with rows, a triple."""
-    _need_gpu_as(store, torch.uint8, 'store')
-    _need_gpu_as(slots, torch.int64, 'slots')
-    _need_gpu_as(index, torch.int64, 'index')
-    if rows is not None:
-        _need_gpu_as(rows, torch.int32, 'rows')
-    h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
-    if store.dim() != 1 or slots.dim() != 2 or index.dim() != 1 or index.numel() == 0 or h <= 0 or w <= 0:
-        raise ValueError('gather_items_u8: store (bytes,), slots (N,K), index (B,) with B > 0, positive size')
-    N, K = slots.shape
-    if not 1 <= K <= GATHER_ITEMS_MAX_K or N == 0:
-        raise ValueError('gather_items_u8: slots must be (N,K) with N > 0 and 1 <= K <= %d' % GATHER_ITEMS_MAX_K)
-    B, dev = index.numel(), store.device
-    if rows is not None and (rows.dim() != 2 or rows.shape[0] != N or rows.shape[1] == 0):
-        raise ValueError('gather_items_u8: rows must be (N,V) with the N of slots and V > 0')
-    V = 0 if rows is None else rows.shape[1]
-    if slots.device != dev or index.device != dev or (rows is not None and rows.device != dev):
-        raise ValueError('gather_items_u8: store, slots, index and rows must lie on one device')
-    shapes = [(B, 3, h, w), (B, K - 1, 3, h, w)] + ([(B, V)] if V else [])
-    dtypes = [torch.float32, torch.float32, torch.int32]
-    if out is None:
-        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
-    else:
-        out = tuple(out)
-        if len(out) != len(shapes) or not all(torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == d and t.is_contiguous()
-                                              and tuple(t.shape) == s for t, s, d in zip(out, shapes, dtypes)):
-            raise ValueError('gather_items_u8: out must be contiguous GPU tensors of shapes %s (fp32, fp32, int32)' % (shapes,))
-    rc = _lib.load().t2o_gather_items_u8_to_f32(_ptr(store), _ptr(slots), _ptr(index), N, K, B, h, w, _ptr(out[0]),
-                                                _ptr(out[1]) if K > 1 else None, _ptr(rows), V, _ptr(out[2]) if V else None,
-                                                _stream(dev))
-    _lib.check(rc, 't2o_gather_items_u8_to_f32')
-    return out
+    return _gather('gather_items_u8', GATHER_ITEMS_MAX_K, True, store, slots, index, size, rows, out)
 
 
 # ---- 8-bit replay (t2o_replay.hip): a known operator list on uint8 pictures at their native size ----
@@ -2055,10 +2042,24 @@ def replay_status(rc, what='t2o_replay_u8'):
     raise {1: ValueError, 2: NotImplementedError}.get(rc, RuntimeError)(msg)
 
 
-def _replay_args(who, src_u8, jobs, params, out):
-    """What replay_u8 and replay_u8_masked check alike, so that a wrong offset or size is a Python error and never a GPU fault:
-    the source, every job's (src_offset, out_offset, h, w, ...) against source and output, `out` (allocated to fit when None) and
-    params -> (jobs as tuples, out, contiguous params)."""
+REPLAY_MAX_MASKS, REPLAY_SHARPNESS = 4, 6             # (the executor index of the sharpness, data.ACTIONS)
+
+
+def replay_mask_table(jobs):
+    """The (J, 8) per-step mask indices of `jobs` (6-tuples, see replay_u8_masked) as the ctypes int array
+    t2o_replay_u8_masked takes: -1 where a job's mask_of is shorter than 8."""
+    arr = (ctypes.c_int * (REPLAY_MAX_STEPS * len(jobs)))(*([-1] * (REPLAY_MAX_STEPS * len(jobs))))
+    for j, job in enumerate(jobs):
+        for k, i in enumerate(list(job[5])[:REPLAY_MAX_STEPS]):
+            arr[REPLAY_MAX_STEPS * j + k] = int(i)
+    return arr
+
+
+def _replay(who, masked, src_u8, jobs, params, masks_u8=None, mask_offsets=(), out=None, five_ok=False):
+    """replay_u8, replay_u8_masked and replay_u8_stencils: who = the C entry point without its t2o_; masked: jobs carry mask_of
+    and the entry point takes masks; five_ok: a 5-tuple job names no mask.  Checked here, so that a wrong offset or size is a
+    Python error and never a GPU fault: the source, every job against source and output, `out` (allocated to fit when None),
+    params, and with masks their number, their buffer, each mask_of against its list and each named mask against the buffer."""
     if not (torch.is_tensor(src_u8) and src_u8.is_cuda and src_u8.dtype == torch.uint8 and src_u8.is_contiguous()):
         raise ValueError('%s: src must be a contiguous uint8 GPU tensor' % who)
     jobs = [tuple(j) for j in jobs]
@@ -2077,7 +2078,32 @@ def _replay_args(who, src_u8, jobs, params, out):
         params = params.contiguous()
         if tuple(params.shape) != (len(jobs), REPLAY_MAX_STEPS, PARAM_PAD):
             raise ValueError('%s: params must be (J, 8, 24), got %s' % (who, tuple(params.shape)))
-    return jobs, out, params
+    if not masked:
+        tables = (replay_jobs(jobs), len(jobs), _ptr(params))
+    else:
+        if five_ok:
+            for j, job in enumerate(jobs):
+                if len(job) not in (5, 6):
+                    raise ValueError('%s: job %d has %d fields, 5 or 6 are taken' % (who, j, len(job)))
+            jobs = [job if len(job) == 6 else job + ([-1] * len(job[4]),) for job in jobs]
+        mask_offsets = [int(o) for o in mask_offsets]
+        if len(mask_offsets) > REPLAY_MAX_MASKS:
+            raise ValueError('%s: at most 4 masks per launch, got %d' % (who, len(mask_offsets)))
+        if mask_offsets and not (torch.is_tensor(masks_u8) and masks_u8.is_cuda and masks_u8.dtype == torch.uint8
+                                 and masks_u8.is_contiguous() and masks_u8.device == src_u8.device):
+            raise ValueError('%s: masks must be a contiguous uint8 GPU tensor on the source\'s device' % who)
+        for j, (_, _, h, w, ops, mask_of) in enumerate(jobs):
+            if len(mask_of) > len(ops):
+                raise ValueError('%s: job %d names %d masks for %d steps' % (who, j, len(mask_of), len(ops)))
+            for i in mask_of if h > 0 and w > 0 else ():             # (an empty picture: the library refuses it)
+                if 0 <= i < len(mask_offsets) and not (0 <= mask_offsets[i] and mask_offsets[i] + h * w <= masks_u8.numel()):
+                    raise ValueError('%s: job %d reads mask %d outside the %d-byte mask buffer' % (who, j, i, masks_u8.numel()))
+        offs = (ctypes.c_longlong * max(len(mask_offsets), 1))(*mask_offsets)
+        tables = (replay_jobs([j[:5] for j in jobs]), replay_mask_table(jobs), len(jobs), _ptr(params),
+                  _ptr(masks_u8) if mask_offsets else None, offs, len(mask_offsets))
+    rc = getattr(_lib.load(), 't2o_' + who)(_ptr(src_u8), _ptr(out), *tables, _stream(src_u8.device))
+    replay_status(rc, 't2o_' + who)
+    return out
 
 
 def replay_u8(src_u8, jobs, params, out=None):
@@ -2087,23 +2113,7 @@ def replay_u8(src_u8, jobs, params, out=None):
     GPU; None when no job applies an operator) as Operator.execute does with specified_param, and writes at byte out_offset of
     `out` (allocated to fit when None).  The bytes equal resize_u8 at the picture's size -> operator_apply per step ->
     to_u8_hwc.  Returns out (1-D uint8)."""
-    jobs, out, params = _replay_args('replay_u8', src_u8, jobs, params, out)
-    rc = _lib.load().t2o_replay_u8(_ptr(src_u8), _ptr(out), replay_jobs(jobs), len(jobs), _ptr(params), _stream(src_u8.device))
-    replay_status(rc)
-    return out
-
-
-REPLAY_MAX_MASKS = 4
-
-
-def replay_mask_table(jobs):
-    """The (J, 8) per-step mask indices of `jobs` (6-tuples, see replay_u8_masked) as the ctypes int array
-    t2o_replay_u8_masked takes: -1 where a job's mask_of is shorter than 8."""
-    arr = (ctypes.c_int * (REPLAY_MAX_STEPS * len(jobs)))(*([-1] * (REPLAY_MAX_STEPS * len(jobs))))
-    for j, job in enumerate(jobs):
-        for k, i in enumerate(list(job[5])[:REPLAY_MAX_STEPS]):
-            arr[REPLAY_MAX_STEPS * j + k] = int(i)
-    return arr
+    return _replay('replay_u8', False, src_u8, jobs, params, out=out)
 
 
 def replay_u8_masked(src_u8, jobs, params, masks_u8, mask_offsets, out=None):
@@ -2114,25 +2124,7 @@ def replay_u8_masked(src_u8, jobs, params, masks_u8, mask_offsets, out=None):
     computes clamp(o * m + x * (1 - m), 0, 1) with m = byte / 255 where it names a mask, clamp(o, 0, 1) where it names
     none.  The bytes equal resize_u8 at the picture's size -> operator_apply(op, x, param, mask (1,1,h,w) fp32) per step ->
     to_u8_hwc.  Returns out (1-D uint8)."""
-    jobs, out, params = _replay_args('replay_u8_masked', src_u8, jobs, params, out)
-    mask_offsets = [int(o) for o in mask_offsets]
-    if len(mask_offsets) > REPLAY_MAX_MASKS:
-        raise ValueError('replay_u8_masked: at most 4 masks per launch, got %d' % len(mask_offsets))
-    if mask_offsets and not (torch.is_tensor(masks_u8) and masks_u8.is_cuda and masks_u8.dtype == torch.uint8
-                             and masks_u8.is_contiguous() and masks_u8.device == src_u8.device):
-        raise ValueError('replay_u8_masked: masks must be a contiguous uint8 GPU tensor on the source\'s device')
-    for j, (_, _, h, w, ops, mask_of) in enumerate(jobs):
-        if len(mask_of) > len(ops):
-            raise ValueError('replay_u8_masked: job %d names %d masks for %d steps' % (j, len(mask_of), len(ops)))
-        for i in mask_of if h > 0 and w > 0 else ():             # (an empty picture: the library refuses it)
-            if 0 <= i < len(mask_offsets) and not (0 <= mask_offsets[i] and mask_offsets[i] + h * w <= masks_u8.numel()):
-                raise ValueError('replay_u8_masked: job %d reads mask %d outside the %d-byte mask buffer' % (j, i, masks_u8.numel()))
-    offs = (ctypes.c_longlong * max(len(mask_offsets), 1))(*mask_offsets)
-    rc = _lib.load().t2o_replay_u8_masked(_ptr(src_u8), _ptr(out), replay_jobs([j[:5] for j in jobs]), replay_mask_table(jobs),
-                                          len(jobs), _ptr(params), _ptr(masks_u8) if mask_offsets else None, offs,
-                                          len(mask_offsets), _stream(src_u8.device))
-    replay_status(rc, 't2o_replay_u8_masked')
-    return out
+    return _replay('replay_u8_masked', True, src_u8, jobs, params, masks_u8, mask_offsets, out)
 
 
 def replay_u8_stencils(src_u8, jobs, params, masks_u8=None, mask_offsets=(), out=None):
@@ -2143,29 +2135,23 @@ def replay_u8_stencils(src_u8, jobs, params, masks_u8=None, mask_offsets=(), out
     its input at the centre.  The bytes equal resize_u8 at the picture's size -> operator_apply(op, x, param[, mask]) per
     step -> to_u8_hwc.  Lists with at most one sharpness give replay_u8's / replay_u8_masked's bytes, at a higher cost
     (the window is recomputed on a ring of one pixel per sharpness).  Returns out (1-D uint8)."""
-    jobs, out, params = _replay_args('replay_u8_stencils', src_u8, jobs, params, out)
-    for j, job in enumerate(jobs):
-        if len(job) not in (5, 6):
-            raise ValueError('replay_u8_stencils: job %d has %d fields, 5 or 6 are taken' % (j, len(job)))
-    jobs = [job if len(job) == 6 else job + ([-1] * len(job[4]),) for job in jobs]
-    mask_offsets = [int(o) for o in mask_offsets]
-    if len(mask_offsets) > REPLAY_MAX_MASKS:
-        raise ValueError('replay_u8_stencils: at most 4 masks per launch, got %d' % len(mask_offsets))
-    if mask_offsets and not (torch.is_tensor(masks_u8) and masks_u8.is_cuda and masks_u8.dtype == torch.uint8
-                             and masks_u8.is_contiguous() and masks_u8.device == src_u8.device):
-        raise ValueError('replay_u8_stencils: masks must be a contiguous uint8 GPU tensor on the source\'s device')
-    for j, (_, _, h, w, ops, mask_of) in enumerate(jobs):
-        if len(mask_of) > len(ops):
-            raise ValueError('replay_u8_stencils: job %d names %d masks for %d steps' % (j, len(mask_of), len(ops)))
-        for i in mask_of if h > 0 and w > 0 else ():             # (an empty picture: the library refuses it)
-            if 0 <= i < len(mask_offsets) and not (0 <= mask_offsets[i] and mask_offsets[i] + h * w <= masks_u8.numel()):
-                raise ValueError('replay_u8_stencils: job %d reads mask %d outside the %d-byte mask buffer' % (j, i, masks_u8.numel()))
-    offs = (ctypes.c_longlong * max(len(mask_offsets), 1))(*mask_offsets)
-    rc = _lib.load().t2o_replay_u8_stencils(_ptr(src_u8), _ptr(out), replay_jobs([j[:5] for j in jobs]), replay_mask_table(jobs),
-                                            len(jobs), _ptr(params), _ptr(masks_u8) if mask_offsets else None, offs,
-                                            len(mask_offsets), _stream(src_u8.device))
-    replay_status(rc, 't2o_replay_u8_stencils')
-    return out
+    return _replay('replay_u8_stencils', True, src_u8, jobs, params, masks_u8, mask_offsets, out, five_ok=True)
+
+
+def replay_u8_pick(jobs):
+    """The name of the wrapper that serves a launch of `jobs` (a list) -- THE rule, held here only: replay_u8_stencils for the whole
+    launch when some job repeats the sharpness, else the cheaper kernel: replay_u8_masked for 6-tuple jobs, else replay_u8."""
+    if any(sum(op == REPLAY_SHARPNESS for op in job[4]) >= 2 for job in jobs):
+        return 'replay_u8_stencils'
+    return 'replay_u8_masked' if any(len(job) == 6 for job in jobs) else 'replay_u8'
+
+
+def replay_u8_any(src_u8, jobs, params, masks_u8=None, mask_offsets=(), out=None):
+    """replay_u8, replay_u8_masked or replay_u8_stencils, whichever replay_u8_pick names for `jobs`, with that wrapper's
+    arguments and result.  (The wrappers are looked up by name at call time.)"""
+    jobs = [tuple(j) for j in jobs]
+    name = replay_u8_pick(jobs)
+    return globals()[name](src_u8, jobs, params, *((out,) if name == 'replay_u8' else (masks_u8, mask_offsets, out)))
 
 
 # ---- local-edit masks (t2o_mask.hip): run-length masks resized and unioned on the device; the per-step mask select ----
