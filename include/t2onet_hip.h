@@ -892,6 +892,56 @@ size_t t2o_feather_workspace_bytes(const t2o_feather_job_t* jobs, int J);
 int t2o_feather_u8(const unsigned char* src, unsigned char* out, const t2o_feather_job_t* jobs, int J, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* ---- the mask planes of a local edit made from a RULE on the device (t2o_select.hip): no painted file, no host-built
+ * plane, no upload of h * w bytes per plane.  Job j writes the (h,w) uint8 plane at out + out_offset (any byte
+ * alignment; no byte outside the plane is written) from the uint8 HWC RGB photo of the same size at src + src_offset
+ * (any byte alignment).  A SELECTION is n_terms = 1..4 terms; term k gives a weight t_k in 0..255 per pixel,
+ * t_k := 255 - t_k when `invert` is 1; m = t_1, then m = (m * t_k + 127) / 255 left to right.  INTEGER arithmetic, every
+ * division a floor division of non-negative integers.  With R, G, B the pixel's bytes, mx / mn their max / min:
+ *   L = (69 R + 172 G + 15 B + 128) >> 8                       luminance 0.27 / 0.67 / 0.06 in 8 fractional bits, 0..255
+ *   S = 0 if mx = 0, else (255 (mx - mn) + mx / 2) / mx        saturation, 0..255
+ *   H: d = mx - mn; undefined for d = 0; if mx = R: n = G - B, base 0; else if mx = G: n = B - R, base 512; else
+ *      n = R - G, base 1024;  q = (512 (n + d) + d) / (2 d) - 256;  H = (base + q) mod 1536        six sectors of 256:
+ *      red 0, yellow 256, green 512, cyan 768, blue 1024, magenta 1280
+ *   ramp(dist, soft) = 255 at dist = 0, 0 at dist >= soft, else (255 (soft - dist) + soft / 2) / soft  (soft = 0: a step)
+ * Kinds and their parameters p[0..3]:
+ *   T2O_SELECT_LUM, T2O_SELECT_SAT  lo, hi, soft: ramp(how far L / S lies outside [lo, hi], soft); 0 <= lo <= hi <= 255,
+ *                      0 <= soft <= 255
+ *   T2O_SELECT_HUE     lo, hi, soft: the arc runs upward from lo to hi modulo 1536 (wrapping when hi < lo); ramp(circular
+ *                      distance of H to the arc, soft); an undefined hue weighs 0 (before inversion); lo, hi in 0..1535,
+ *                      0 <= soft <= 768
+ *   T2O_SELECT_LINEAR  X0, Y0, X1, Y1 (pixels, not equal): num = (x - X0) DX + (y - Y0) DY, den = DX^2 + DY^2; 255 for
+ *                      num <= 0, 0 for num >= den, else (255 (den - num) + den / 2) / den
+ *   T2O_SELECT_RADIAL  CX, CY, RI, RO (0 <= RI < RO): d2 = (x - CX)^2 + (y - CY)^2, den = RO^2 - RI^2; 255 for d2 <= RI^2,
+ *                      0 for d2 >= RO^2, else (255 (RO^2 - d2) + den / 2) / den -- linear in the squared distance
+ *   T2O_SELECT_PLANE   the byte of the (h,w) uint8 plane at src + plane_offset (any byte alignment) is the weight: a
+ *                      painted mask intersected with a rule
+ * Position terms compute in 64 bits; they need h, w <= 65535 and parameters within +-131070.
+ * jobs: HOST array of 1 <= J <= 4, copied into the kernel arguments; jobs may differ in size and may share a photo.  ONE
+ * launch: a lane owns four neighbouring pixels of a plane taken as a stream of h * w pixels, 12 source bytes in, one
+ * aligned plane dword out, single bytes at the two ends of a misaligned plane; 3 + 1 bytes of traffic per pixel plus 1
+ * per plane term, the 3 only for a job with a lum, sat or hue term (the photo is not read otherwise).  No workspace, no allocation, no host synchronisation, no float, no atomics; deterministic, capturable.
+ * The caller guarantees that offsets and sizes lie inside src / out.
+ * T2O_EINVAL, before any launch: null pointers, J or n_terms outside 1..4, non-positive sizes, h * w >= 2^31, a position
+ * term with h or w above 65535, negative offsets, an unknown kind, invert other than 0 / 1, parameters outside the
+ * ranges above, a destination that overlaps another destination or (by address: src and out may be one buffer) any
+ * photo or plane term of the call. */
+#define T2O_SELECT_MAX_JOBS 4
+#define T2O_SELECT_MAX_TERMS 4
+enum { T2O_SELECT_LUM = 0, T2O_SELECT_SAT = 1, T2O_SELECT_HUE = 2, T2O_SELECT_LINEAR = 3, T2O_SELECT_RADIAL = 4, T2O_SELECT_PLANE = 5 };
+typedef struct {
+  int kind, invert;
+  int p[4];                           /* see the kinds above; unused entries are ignored */
+  long long plane_offset;             /* T2O_SELECT_PLANE: first byte of the plane, counted from src */
+} t2o_select_term_t;
+typedef struct {
+  long long src_offset, out_offset;   /* first byte of the photo / the destination plane, counted from src / out */
+  int h, w;
+  int n_terms, reserved;
+  t2o_select_term_t terms[T2O_SELECT_MAX_TERMS];
+} t2o_select_job_t;
+int t2o_select_u8(const unsigned char* src, unsigned char* out, const t2o_select_job_t* jobs, int J, void* stream);
+
 /* ---- the metrics of the test loop in one call: utils/eval.py:50-60 (ImageEvaluator.update: input / output L1 and SSIM),
  * utils/ssim/__init__.py:20-40 (the SSIM itself) and test_seq2seqL1.py:60-74 (the END-image select and the two L1
  * distances the loop averages).  imgs: HOST array of 1 <= T <= 8 device pointers to (B,C,H,W) step images, first: device

@@ -13,7 +13,15 @@ replay at its native size (with --multi_img: one job per prefix of the list), at
 most one sharpness goes through functional.replay_u8, any other through functional.replay_u8_stencils
 (functional.replay_u8_any chooses per launch).  The files of each
 photo are edit_cli's (write_outputs); the new record takes 'request' from the source record and names it under 'record'.
-Global edits only: masks stay with edit_cli --mask.
+
+A record with 'select' (edit_cli --select: {operator name or 'all': TERM[+TERM...]}) and optionally 'feather' ({one of
+those names: sigma in pixels}; as in edit_cli, 'all' is the unnamed --feather and softens every plane that has no sigma
+of its own) is applied LOCALLY: a selection is a rule in units of the frame, so every photo gets its
+own planes at its own size, computed on the device.  The photos are grouped so that a group names at most 4 planes; per
+group ONE functional.select_u8 launch writes the planes, functional.feather_u8's two launches soften them if asked, and
+ONE functional.replay_u8_any launch replays the list under them.  The new records carry 'select' and 'feather' along.
+Painted masks do not carry from photo to photo: a record with 'masks' and no 'select' is replayed globally, as before,
+and a record that has both is refused.
 """
 import argparse
 import json
@@ -25,6 +33,7 @@ import torch
 from .data import ACT2PN, ACTIONS, decode_image
 
 MAX_STEPS, MAX_JOBS, PARAM_PAD = 8, 64, 24          # functional.REPLAY_MAX_STEPS, REPLAY_MAX_JOBS, PARAM_PAD (checked in apply_record)
+MAX_PLANES = 4                                      # functional.REPLAY_MAX_MASKS (checked in apply_record_local)
 
 
 def parse_record(record):
@@ -53,6 +62,96 @@ def parse_record(record):
             raise ValueError('record: operation %d: %s has a value that is not a number: %r' % (k, name, values))
         ops.append(ACTIONS.index(name))
     return str(info.get('request', '')), ops, params
+
+
+def parse_local(record):
+    """The local part of a record -> None (a global edit), or (select, feather): {operator name or 'all': TERM[+TERM...] as
+    edit_cli recorded it} and {one of those names: sigma}.  Raises ValueError: a 'select' beside 'masks', a spec that does
+    not parse, a feather that names no selection."""
+    from .edit_cli import parse_feather_args, parse_select_args
+    info = record[0] if isinstance(record, list) and record else record
+    select = info.get('select') if isinstance(info, dict) else None
+    if select is None:
+        return None
+    if info.get('masks'):
+        raise ValueError('record: it has \'select\' and \'masks\': a rule intersected with a painted plane belongs to one photo '
+                         'and is not carried to others (edit_cli --mask stays with its photo)')
+    if not (isinstance(select, dict) and select and all(isinstance(k, str) and isinstance(v, str) for k, v in select.items())):
+        raise ValueError('record: \'select\' is {operator name or \'all\': TERM[+TERM...]}, got %r' % (select,))
+    rules = parse_select_args([text if name == 'all' else '%s=%s' % (name, text) for name, text in select.items()])
+    feather = info.get('feather') or {}
+    if not isinstance(feather, dict):
+        raise ValueError('record: \'feather\' is {name: sigma}, got %r' % (feather,))
+    sigmas = parse_feather_args([str(v) if name == 'all' else '%s=%s' % (name, v) for name, v in feather.items()], rules)
+    return rules, sigmas
+
+
+def local_planes(ops, select, feather):
+    """Which planes a photo needs for `ops` under parse_local's (select, feather) -> ([(terms in user units, sigma)],
+    mask_of): the distinct planes, and per step the plane's number or -1.  A named entry wins over 'all', in select and in
+    feather alike: an 'all' sigma stands for every plane that has none of its own (edit_cli.feather_argument)."""
+    from .edit_cli import parse_select_terms
+    planes, mask_of = [], []
+    for op in ops:
+        name = ACTIONS[op] if ACTIONS[op] in select else 'all'
+        if name not in select:
+            mask_of.append(-1)
+            continue
+        plane = (tuple(parse_select_terms(select[name])), float(feather.get(name, feather.get('all', 0.0))))
+        if plane not in planes:
+            planes.append(plane)
+        mask_of.append(planes.index(plane))
+    if len(planes) > MAX_PLANES:
+        raise ValueError('record: the operations name %d distinct selections, the replay takes %d' % (len(planes), MAX_PLANES))
+    return planes, mask_of
+
+
+def apply_record_local(images, ops, params, select, feather, multi_img=False, device=None):
+    """apply_record under the selections of parse_local: the same result layout.  One upload; per group of photos that
+    together name at most 4 planes: one select_u8 launch, feather_u8 where a sigma is given, one replay launch."""
+    from . import functional as T
+    from .edit import select_terms
+    assert (MAX_STEPS, MAX_JOBS, PARAM_PAD, MAX_PLANES) == (T.REPLAY_MAX_STEPS, T.REPLAY_MAX_JOBS, T.PARAM_PAD, T.REPLAY_MAX_MASKS)
+    planes, mask_of = local_planes(ops, select, feather)
+    if not planes:                                                    # no operation of the list is selected for
+        return apply_record(images, ops, params, multi_img, device)
+    shapes = [tuple(int(v) for v in im.shape[:2]) for im in images]
+    rules = [[select_terms(terms, h, w, 'record') for terms, _ in planes] for h, w in shapes]      # before any device use
+    if device is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    buffer, descs = T.pack_u8(images)
+    dev_buffer, _, descs, _keep = T.upload_packed(buffer, descs, device)
+    offsets = [int(d['offset']) for d in descs]
+    row = torch.zeros(MAX_STEPS, PARAM_PAD)
+    row[:len(ops)] = torch.as_tensor(np.asarray(params, np.float32).reshape(len(ops), PARAM_PAD))
+    row = row.to(device)
+    prefixes = list(range(1, len(ops) + 1)) if multi_img else [len(ops)]
+    steps = []
+    per = MAX_PLANES // len(planes)                                   # photos of a group
+    for a in range(0, len(images), per):
+        group = list(range(a, min(a + per, len(images))))
+        sel_jobs, soft_jobs, jobs, where, at, pos = [], [], [], {}, 0, 0
+        for i in group:
+            h, w = shapes[i]
+            for k, (_, sigma) in enumerate(planes):
+                where[i, k] = len(sel_jobs)
+                sel_jobs.append((offsets[i], at, h, w, rules[i][k]))
+                if sigma > 0.0:
+                    soft_jobs.append((at, at, h, w, sigma))
+                at += h * w
+            for n in prefixes:
+                jobs.append((offsets[i], pos, h, w, list(ops[:n]), [where[i, k] if k >= 0 else -1 for k in mask_of[:n]]))
+                pos += 3 * h * w
+        plane_buffer = T.select_u8(dev_buffer, sel_jobs)
+        if soft_jobs:
+            T.feather_u8(plane_buffer, soft_jobs)
+        out = T.replay_u8_any(dev_buffer, jobs, row.unsqueeze(0).expand(len(jobs), -1, -1).contiguous(), plane_buffer,
+                              [job[1] for job in sel_jobs]).cpu().numpy()
+        for i in group:
+            h, w = shapes[i]
+            mine = [job for job in jobs if job[0] == offsets[i]]
+            steps.append(np.stack([out[job[1]:job[1] + 3 * h * w].reshape(h, w, 3) for job in mine]))
+    return steps
 
 
 def pick_wrapper(ops):
@@ -110,12 +209,19 @@ def main(argv=None):
     ap.add_argument('--save_dir', default='output/demo_output')
     args = ap.parse_args(argv)
     with open(args.record) as f:
-        request, ops, params = parse_record(json.load(f))             # before any decode or device use
+        record = json.load(f)
+    request, ops, params = parse_record(record)                       # before any decode or device use
+    local = parse_local(record)
     images = [decode_image(p) for p in args.img]
     from .edit_cli import write_outputs
     infos = []
-    for path, img, steps in zip(args.img, images, apply_record(images, ops, params, args.multi_img)):
-        info = write_outputs(args.save_dir, path, request, img, steps, ops, params, args.multi_img)
+    if local is None:
+        results, carried = apply_record(images, ops, params, args.multi_img), {}
+    else:
+        results = apply_record_local(images, ops, params, local[0], local[1], args.multi_img)
+        carried = {'select': local[0], 'feather': local[1] or None}
+    for path, img, steps in zip(args.img, images, results):
+        info = write_outputs(args.save_dir, path, request, img, steps, ops, params, args.multi_img, **carried)
         info['record'] = args.record
         name = os.path.splitext(os.path.basename(path))[0]
         with open(os.path.join(args.save_dir, name, name + '.json'), 'w') as f:

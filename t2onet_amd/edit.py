@@ -80,6 +80,131 @@ def checked_feather(feather, masks):
     return {plane: sigma for plane, sigma in by_plane.items() if sigma > 0.0}
 
 
+def _round_unit(v, scale):
+    """floor(v * scale + 0.5) in double: the host rounding of a selection's user units."""
+    return int(np.floor(np.float64(v) * np.float64(scale) + 0.5))
+
+
+def _select_numbers(term, who):
+    if not (isinstance(term, (tuple, list)) and term and isinstance(term[0], str)):
+        raise ValueError('%s: select term %r is not (\'[!]kind\', numbers...)' % (who, term))
+    try:
+        values = [float(v) for v in term[1:]]
+    except (TypeError, ValueError):
+        raise ValueError('%s: select term %r has a value that is not a number' % (who, term))
+    if not all(np.isfinite(values)):
+        raise ValueError('%s: select term %r has a value that is not finite' % (who, term))
+    return term[0].lstrip('!'), int(term[0].startswith('!')), values
+
+
+def check_select_terms(terms, who='edit_image'):
+    """The checks of a selection in user units that do not need the photo's size; raises ValueError naming the term.
+    terms: 1 to 4 of ('[!]lum' | '[!]sat', lo, hi[, soft]) in fractions [0, 1], ('[!]hue', lo, hi[, soft]) in degrees
+    [0, 360) with soft <= 180, ('[!]linear', x0, y0, x1, y1) in fractions of w - 1 / h - 1, ('[!]radial', cx, cy, rin, rout)
+    with the radii in fractions of min(h, w); a leading '!' inverts the term."""
+    terms = list(terms) if isinstance(terms, (tuple, list)) else None
+    if not terms or len(terms) > T.SELECT_MAX_TERMS:
+        raise ValueError('%s: a selection is a list of 1 to %d terms' % (who, T.SELECT_MAX_TERMS))
+    for term in terms:
+        kind, _, v = _select_numbers(term, who)
+        if kind in ('lum', 'sat', 'hue'):
+            if len(v) not in (2, 3):
+                raise ValueError('%s: select term %r takes lo, hi and an optional softness' % (who, term))
+            soft = v[2] if len(v) == 3 else 0.0
+            if kind == 'hue':
+                if not (0.0 <= v[0] < 360.0 and 0.0 <= v[1] < 360.0 and 0.0 <= soft <= 180.0):
+                    raise ValueError('%s: select term %r: hue bounds lie in [0, 360) degrees, the softness in [0, 180]' % (who, term))
+            elif not (0.0 <= v[0] <= v[1] <= 1.0 and 0.0 <= soft <= 1.0):
+                raise ValueError('%s: select term %r: 0 <= lo <= hi <= 1 and a softness in [0, 1]' % (who, term))
+        elif kind in ('linear', 'radial'):
+            if len(v) != 4:
+                raise ValueError('%s: select term %r takes four numbers' % (who, term))
+            if not all(-1.0 <= a <= 2.0 for a in (v if kind == 'linear' else v[:2])):
+                raise ValueError('%s: select term %r: positions lie in [-1, 2] (fractions of the frame)' % (who, term))
+            if kind == 'linear' and v[:2] == v[2:]:
+                raise ValueError('%s: select term %r: the two end points are equal' % (who, term))
+            if kind == 'radial' and not 0.0 <= v[2] < v[3] <= 2.0:
+                raise ValueError('%s: select term %r: 0 <= rin < rout <= 2 (fractions of the short side)' % (who, term))
+        else:
+            raise ValueError('%s: select term %r: the kind is one of lum, sat, hue, linear, radial' % (who, term))
+    return terms
+
+
+def select_terms(terms, h, w, who='edit_image'):
+    """A selection in user units (check_select_terms) -> the integer terms of functional.select_u8 for an (h, w) photo:
+    floor(v * scale + 0.5) in double with scale 255 for lum / sat, 1536 / 360 for hue (bounds modulo 1536), w - 1 and
+    h - 1 for positions, min(h, w) for radii.  A gradient that collapses on this size is a ValueError."""
+    if h > 65535 or w > 65535:
+        raise ValueError('%s: a selection takes photos up to 65535 pixels a side, got %d x %d' % (who, w, h))
+    out = []
+    for term in check_select_terms(terms, who):
+        kind, invert, v = _select_numbers(term, who)
+        if kind in ('lum', 'sat'):
+            p = [_round_unit(a, 255.0) for a in (v if len(v) == 3 else v + [0.0])]
+        elif kind == 'hue':
+            scale = 1536.0 / 360.0
+            v = v if len(v) == 3 else v + [0.0]
+            p = [_round_unit(v[0], scale) % 1536, _round_unit(v[1], scale) % 1536, _round_unit(v[2], scale)]
+        elif kind == 'linear':
+            p = [_round_unit(v[0], w - 1), _round_unit(v[1], h - 1), _round_unit(v[2], w - 1), _round_unit(v[3], h - 1)]
+            if p[:2] == p[2:]:
+                raise ValueError('%s: select term %r: the end points fall on one pixel of a %d x %d photo' % (who, term, w, h))
+        else:
+            p = [_round_unit(v[0], w - 1), _round_unit(v[1], h - 1), _round_unit(v[2], min(h, w)), _round_unit(v[3], min(h, w))]
+            if not p[2] < p[3]:
+                raise ValueError('%s: select term %r: the radii fall together on a %d x %d photo' % (who, term, w, h))
+        out.append((kind, invert) + tuple(p))
+    return out
+
+
+def _key_targets(key, what):
+    if key == 'all':
+        return [i - 3 for i, allowed in enumerate(OP_MASK) if allowed and i >= 3]
+    if isinstance(key, (int, np.integer)) and not isinstance(key, bool) and 0 <= int(key) < len(T.OP_NPARAM):
+        return [int(key)]
+    raise ValueError('edit_image: %s key %r is neither \'all\' nor an executor operator index 0..7' % (what, key))
+
+
+def select_plan(select, masks, feather, h, w):
+    """The planes of an edit_image call that gives `select` -- checked without any device use.  select: {executor operator
+    index or 'all': selection in user units}, keyed like masks.  Every key of select or masks gets a plane: its selection,
+    multiplied by its painted mask when the SAME key has one (a 'plane' term: the intersection); a key with only a painted
+    mask is a one-term 'plane' job.  Keys whose rule and painted plane agree share a plane.  Returns (painted, specs, by_op,
+    sigma_of): the distinct painted planes to upload, per plane (integer terms, number of its painted plane or None),
+    {operator index: plane number} ('all' first, an entry for one operator wins), {plane number: sigma > 0}."""
+    if not isinstance(select, dict) or not select:
+        raise ValueError('edit_image: select is {executor operator index or \'all\': [terms]}')
+    masks = masks or {}
+    painted, slot_of = [], {}
+    for key in masks:
+        _key_targets(key, 'mask')
+        a = masks[key].numpy() if torch.is_tensor(masks[key]) else np.asarray(masks[key])
+        if a.dtype != np.uint8 or a.shape != (h, w):
+            raise ValueError('edit_image: mask %r must be uint8 (%d, %d), the photo\'s size; got %s %s' % (key, h, w, a.dtype, a.shape))
+        if id(masks[key]) not in slot_of:
+            slot_of[id(masks[key])] = len(painted)
+            painted.append(np.ascontiguousarray(a))
+    specs, by_op, tokens = [], {}, {}
+    for key in sorted(set(select) | set(masks), key=lambda k: (k != 'all', str(k))):      # 'all' first, so that named entries overwrite it
+        targets = _key_targets(key, 'select' if key in select else 'mask')
+        terms = tuple(select_terms(select[key], h, w)) if key in select else ()
+        slot = slot_of[id(masks[key])] if key in masks else None
+        if len(terms) + (slot is not None) > T.SELECT_MAX_TERMS:
+            raise ValueError('edit_image: select %r has %d terms and a painted mask, which counts as one: at most %d'
+                             % (key, len(terms), T.SELECT_MAX_TERMS))
+        if (terms, slot) not in specs:
+            specs.append((terms, slot))
+        for op in targets:
+            by_op[op] = specs.index((terms, slot))
+        tokens[key] = specs.index((terms, slot))
+    if len(specs) > T.REPLAY_MAX_MASKS:
+        raise ValueError('edit_image: %d distinct planes, the replay takes %d' % (len(specs), T.REPLAY_MAX_MASKS))
+    handles = [object() for _ in specs]                               # checked_feather tells planes apart by identity
+    by_handle = checked_feather(feather, {key: handles[no] for key, no in tokens.items()})
+    sigma_of = {no: by_handle[id(hd)] for no, hd in enumerate(handles) if id(hd) in by_handle}
+    return painted, specs, by_op, sigma_of
+
+
 def _append_planes(buffer, planes):
     """The packed photo with the mask planes behind it, so that ONE upload carries both (a plane is 1 byte per pixel: raw
     bytes outside the descriptor table) -> (buffer, byte offset of each plane)."""
@@ -103,7 +228,7 @@ def _proxy_mask_dict(dev_buffer, mask_offsets, by_op, size, proxy_size):
     return [{str(op + 3): [proxies[slot]] for op, slot in by_op.items()}]
 
 
-def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None):
+def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, select=None):
     """img_u8_hwc: the decoded photo, uint8 (h,w,3) RGB (array or CPU tensor); x: (1, L) request token ids.
     Returns (steps_u8, ops, params):
       steps_u8  (max(n,1), h, w, 3) uint8 GPU tensor: picture k is the photo after the first k+1 of the n chosen operators,
@@ -125,24 +250,44 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None):
     feather: None, a standard deviation in pixels of the photo (every plane), or {key of masks: sigma} -- the planes are
     blurred by functional.feather_u8's exact integer Gaussian IN PLACE on the device right after the upload (two launches,
     whatever the number of planes), so that a hard 0/255 selection leaves no seam; the proxy's decision and the native
-    replay see the same soft mask.  Keys that share one plane must agree; feather without masks is an error."""
+    replay see the same soft mask.  Keys that share one plane must agree; feather without masks is an error.
+    select: None, or {executor operator index or 'all': [terms in user units]} keyed like masks -- the planes are RULES
+    (check_select_terms: a luminance, saturation or hue range of the photo itself, a linear or radial gradient over the
+    frame) and are written on the device by ONE functional.select_u8 launch into one tensor, which feather, the proxy and
+    the replay then read as they read the uploaded planes.  A key that also has a painted mask gets the product of the two
+    (the intersection); a key with only a painted mask keeps it; feather may name either.  Nothing but the photo (and the
+    painted planes) is uploaded.  Wrong specifications raise ValueError before any device use (select_plan)."""
     img = T._u8_hwc(img_u8_hwc)
     h, w = img.shape[:2]
-    sigma_of = checked_feather(feather, masks)                  # before any device use
+    plan = select_plan(select, masks, feather, h, w) if select is not None else None       # before any device use
+    sigma_of = checked_feather(feather, masks) if plan is None else {}                       # before any device use
     dev = next(model.parameters()).device
     opt = model.opt
     slot_of = {}
-    planes, by_op = _checked_masks(masks, h, w, slot_of) if masks is not None else ([], {})
+    if plan is not None:
+        planes, specs, by_op, plane_sigma = plan
+    else:
+        planes, by_op = _checked_masks(masks, h, w, slot_of) if masks is not None else ([], {})
+    local = masks is not None or plan is not None
     buffer, descs = T.pack_u8([img])
     mask_offsets = []
     if masks is not None:
         buffer, mask_offsets = _append_planes(buffer, planes)
     dev_buffer, table_ptr, descs, _keep = T.upload_packed(buffer, descs, dev)
-    if sigma_of:
+    mask_buffer = dev_buffer                                    # where the replay and the proxy read the planes
+    if plan is not None:
+        # every plane of the call in ONE launch: a rule, a rule times its painted plane, or a painted plane alone
+        jobs = [(int(descs[0]['offset']), k * h * w, h, w, list(terms) + ([('plane', 0, mask_offsets[slot])] if slot is not None else []))
+                for k, (terms, slot) in enumerate(specs)]
+        mask_buffer = T.select_u8(dev_buffer, jobs)
+        mask_offsets = [k * h * w for k in range(len(specs))]
+        if plane_sigma:
+            T.feather_u8(mask_buffer, [(mask_offsets[k],) * 2 + (h, w, sigma) for k, sigma in plane_sigma.items()])
+    elif sigma_of:
         T.feather_u8(dev_buffer, [(mask_offsets[slot_of[p]],) * 2 + (h, w, sigma) for p, sigma in sigma_of.items()])
     ph, pw = short_side_size(h, w, proxy_short) if min(h, w) > proxy_short else (h, w)
     proxy = T._resize_launch(dev_buffer, table_ptr, 1, ph, pw)
-    mask_dict = None if masks is None else _proxy_mask_dict(dev_buffer, mask_offsets, by_op, (h, w), (ph, pw))
+    mask_dict = _proxy_mask_dict(mask_buffer, mask_offsets, by_op, (h, w), (ph, pw)) if local else None
     x = torch.as_tensor(x, dtype=torch.long).view(1, -1)
     lengths = (x != opt.null_id).sum(1)                      # on the host, before the copy
     was_training = model.training
@@ -163,8 +308,8 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None):
     jobs = [(src_offset, j * nbytes, h, w, ops[:j + 1]) for j in range(J)]       # n = 0: one job with no step
     table = torch.zeros(J, T.REPLAY_MAX_STEPS, T.PARAM_PAD, device=dev)
     table[:, :n] = params
-    if masks is not None:
+    if local:
         mask_of = [by_op.get(op, -1) for op in ops]
         jobs = [job + (mask_of[:j + 1],) for j, job in enumerate(jobs)]
-    out = T.replay_u8_any(dev_buffer, jobs, table, dev_buffer if masks is not None else None, mask_offsets)   # the kernel by the list
+    out = T.replay_u8_any(dev_buffer, jobs, table, mask_buffer if local else None, mask_offsets)   # the kernel by the list
     return out[:J * nbytes].view(J, h, w, 3), ops, params

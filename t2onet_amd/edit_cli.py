@@ -16,6 +16,14 @@ most 4 distinct files.  The record then also holds 'masks': {name or 'all': file
 deviation SIGMA pixels of the photo (at most 64): the soft edge a hard 0/255 selection lacks.  NAME is a name a --mask was
 given under; without a name every mask is feathered.  The record then also holds 'feather': {name or 'all': sigma}.
 
+--select [NAME=]TERM[+TERM...] (repeatable) makes it a local edit WITHOUT a mask file: the plane is a rule, computed on
+the device from the photo's own bytes (edit.edit_image's `select`).  TERM is one of lum:LO:HI[:SOFT], sat:LO:HI[:SOFT]
+(fractions in [0, 1]), hue:LO:HI[:SOFT] (degrees; the arc runs upward from LO to HI and may wrap), linear:X0,Y0:X1,Y1
+(full weight at the first point, none at the second; fractions of the frame), radial:CX,CY:RIN:ROUT (radii in fractions
+of the short side); a leading '!' inverts a term, '+' multiplies terms (at most 4).  NAME is as for --mask; a --select
+and a --mask under the same name are intersected; --feather NAME= may name a --select as well.  The record then also
+holds 'select': {name or 'all': the terms as given}, which apply_cli replays on other photos of any size.
+
 The actor decides on a proxy of the photo (short side --proxy_short, the test loader's 600; a smaller photo is its own
 proxy) and the decision is applied to the photo at its native size by the fused 8-bit replay kernel (edit.edit_image).
 
@@ -87,6 +95,55 @@ def parse_feather_args(specs, named):
     return sigmas
 
 
+def parse_select_terms(spec):
+    """TERM[+TERM...] -> the terms in user units as edit.check_select_terms takes them, [('[!]kind', numbers...)].  Raises
+    ValueError naming the spec."""
+    terms = []
+    for text in spec.split('+'):
+        fields = text.split(':')
+        kind = fields[0].lstrip('!')
+        if kind not in ('lum', 'sat', 'hue', 'linear', 'radial') or len(fields[0]) - len(kind) > 1:
+            raise ValueError('--select %s: %r is not a term (lum, sat, hue, linear or radial, with ! in front to invert)' % (spec, text))
+        shape = {'linear': (2, 2), 'radial': (2, 1, 1)}.get(kind)
+        if shape is None and len(fields) not in (3, 4):
+            raise ValueError('--select %s: %s takes LO:HI[:SOFT], got %r' % (spec, kind, text))
+        if shape is not None and len(fields) != 1 + len(shape):
+            raise ValueError('--select %s: %s takes %s, got %r' % (spec, kind, 'X0,Y0:X1,Y1' if kind == 'linear' else 'CX,CY:RIN:ROUT', text))
+        values = []
+        for k, field in enumerate(fields[1:]):
+            parts = field.split(',')
+            if len(parts) != (shape[k] if shape else 1):
+                raise ValueError('--select %s: %r in %r does not have the numbers %s takes' % (spec, field, text, kind))
+            try:
+                values += [float(v) for v in parts]
+            except ValueError:
+                raise ValueError('--select %s: %r in %r is not a number' % (spec, field, text))
+        terms.append((fields[0],) + tuple(values))
+    return terms
+
+
+def parse_select_args(specs):
+    """--select values ([NAME=]TERM[+TERM...]) -> {operator name or 'all': the terms as given}.  NAME must be one of ACTIONS;
+    every selection is parsed and checked (edit.check_select_terms).  Raises ValueError naming the spec."""
+    from .edit import check_select_terms
+    named = {}
+    for spec in specs or []:
+        head, sep, tail = spec.partition('=')
+        if sep and head not in ACTIONS:
+            raise ValueError('--select %s: %r is not an operator name (one of %s)' % (spec, head, ', '.join(ACTIONS)))
+        name, text = (head, tail) if sep else ('all', spec)
+        if not text:
+            raise ValueError('--select %s: no term given' % spec)
+        check_select_terms(parse_select_terms(text), '--select %s' % spec)
+        named[name] = text
+    return named
+
+
+def select_argument(named):
+    """{name or 'all': terms as given} of parse_select_args -> the `select` argument of edit.edit_image."""
+    return {('all' if name == 'all' else ACTIONS.index(name)): parse_select_terms(text) for name, text in named.items()} or None
+
+
 def feather_argument(sigmas, named):
     """{name or 'all': sigma} of parse_feather_args -> the `feather` argument of edit.edit_image, keyed like the masks
     load_masks returns for `named`.  An unnamed sigma stands for every mask; a named one wins over it.  Two names that
@@ -117,9 +174,9 @@ def load_masks(named, h, w):
     return masks
 
 
-def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, multi_img=False, masks=None, feather=None):
+def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, multi_img=False, masks=None, feather=None, select=None):
     """The files of one edit (see the module docstring); steps_u8: (max(n,1), h, w, 3) uint8 array; masks: {name: file}
-    of a local edit and feather: {name: sigma}, each recorded when given.  Returns the record."""
+    of a local edit, feather: {name: sigma} and select: {name: terms as given}, each recorded when given.  Returns the record."""
     from PIL import Image
     name, ext = os.path.splitext(os.path.basename(img_path))
     out_dir = os.path.join(save_dir, name)
@@ -135,6 +192,8 @@ def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, mu
         info['masks'] = dict(masks)
     if feather:
         info['feather'] = dict(feather)
+    if select:
+        info['select'] = dict(select)
     with open(os.path.join(out_dir, name + '.json'), 'w') as f:
         json.dump([info], f)
     return info
@@ -156,13 +215,22 @@ def main(argv=None):
     ap.add_argument('--feather', action='append', default=None, metavar='[NAME=]SIGMA',
                     help='blur a mask on the device by a Gaussian of SIGMA pixels (at most 64) before it is used; NAME = a name '
                          'a --mask was given under, without it every mask; repeatable')
+    ap.add_argument('--select', action='append', default=None, metavar='[NAME=]TERM[+TERM...]',
+                    help='a local edit by a rule instead of a mask file: lum:LO:HI[:SOFT], sat:LO:HI[:SOFT], hue:LO:HI[:SOFT], '
+                         'linear:X0,Y0:X1,Y1, radial:CX,CY:RIN:ROUT, ! in front inverts, + multiplies; NAME as for --mask; repeatable')
     args = ap.parse_args(argv)
     named = parse_mask_args(args.mask)
-    sigmas = parse_feather_args(args.feather, named)                               # before the model: a wrong value fails early
+    rules = parse_select_args(args.select)
+    planes = dict(named, **rules)                                                  # every name a plane goes by
+    sigmas = parse_feather_args(args.feather, planes)                              # before the model: a wrong value fails early
     img = decode_image(args.img)
     masks = load_masks(named, img.shape[0], img.shape[1]) if named else None       # before the model: a wrong mask fails early
-    feather = feather_argument(sigmas, named)
-    if feather:
+    feather = feather_argument(sigmas, planes)
+    select = select_argument(rules)
+    if select:
+        from .edit import select_plan
+        select_plan(select, masks, feather, img.shape[0], img.shape[1])            # a gradient that collapses on this photo, too many planes
+    elif feather:
         from .edit import checked_feather
         checked_feather(feather, masks)                                            # two names, one file, two sigmas
 
@@ -176,9 +244,9 @@ def main(argv=None):
     model.load_state_dict(torch.load(args.checkpoint, map_location='cpu'), strict=False)      # as the demo (:129)
     model.to(device)
     steps_u8, ops, params = edit_image(model, img, request_to_idx(args.request, vocab2id, opt), args.proxy_short, masks=masks,
-                                      feather=feather)
+                                      feather=feather, select=select)
     info = write_outputs(args.save_dir, args.img, args.request, img, steps_u8.cpu().numpy(), ops, params.cpu(), args.multi_img,
-                         masks=named or None, feather=sigmas or None)
+                         masks=named or None, feather=sigmas or None, select=rules or None)
     print('%s: %s -> %s' % (args.request, ', '.join(n for n, _ in info['operations']) or '(no operator)',
                             os.path.join(args.save_dir, os.path.splitext(os.path.basename(args.img))[0], info['output'])))
     return info

@@ -2385,3 +2385,89 @@ def feather_u8(buffer, jobs, out=None):
     rc = lib.t2o_feather_u8(_ptr(buffer), _ptr(out), table, len(jobs), _ptr(ws), ws.numel(), _stream(buffer.device))
     replay_status(rc, 't2o_feather_u8')
     return out
+
+
+# ---- selections (t2o_select.hip): the mask planes of a local edit computed from a rule, where the photo already lies ----
+
+SELECT_MAX_JOBS, SELECT_MAX_TERMS = 4, 4
+SELECT_KINDS = ('lum', 'sat', 'hue', 'linear', 'radial', 'plane')          # T2O_SELECT_LUM .. T2O_SELECT_PLANE
+
+
+class SelectTerm(ctypes.Structure):
+    """t2o_select_term_t of include/t2onet_hip.h (field for field)."""
+    _fields_ = [('kind', ctypes.c_int), ('invert', ctypes.c_int), ('p', ctypes.c_int * 4), ('plane_offset', ctypes.c_longlong)]
+
+
+class SelectJob(ctypes.Structure):
+    """t2o_select_job_t of include/t2onet_hip.h (field for field)."""
+    _fields_ = [('src_offset', ctypes.c_longlong), ('out_offset', ctypes.c_longlong), ('h', ctypes.c_int), ('w', ctypes.c_int),
+                ('n_terms', ctypes.c_int), ('reserved', ctypes.c_int), ('terms', SelectTerm * SELECT_MAX_TERMS)]
+
+
+def select_jobs(jobs):
+    """jobs: a sequence of (src_offset, out_offset, h, w, terms) -> the ctypes array t2o_select_u8 takes.  A term is
+    (kind, invert, values...) in the INTEGER units of include/t2onet_hip.h, kind a name of SELECT_KINDS or its number:
+    ('lum' | 'sat' | 'hue', invert, lo, hi[, soft]), ('linear', invert, X0, Y0, X1, Y1), ('radial', invert, CX, CY, RI, RO),
+    ('plane', invert, byte offset of the plane in src).  `n_terms` is len(terms) even beyond 4, and an unknown number is
+    passed on, so that the library is the one to refuse them; a wrong number of values is a ValueError here."""
+    arr = (SelectJob * max(len(jobs), 1))()
+    for c, (src_offset, out_offset, h, w, terms) in zip(arr, jobs):
+        c.src_offset, c.out_offset, c.h, c.w, c.n_terms = int(src_offset), int(out_offset), int(h), int(w), len(terms)
+        for t, term in zip(c.terms, list(terms)[:SELECT_MAX_TERMS]):
+            kind, invert, values = term[0], term[1], [int(v) for v in term[2:]]
+            if isinstance(kind, str):
+                if kind not in SELECT_KINDS:
+                    raise ValueError('select_u8: %r is not a term kind (one of %s)' % (kind, ', '.join(SELECT_KINDS)))
+                kind = SELECT_KINDS.index(kind)
+            t.kind, t.invert = int(kind), int(invert)
+            name = SELECT_KINDS[t.kind] if 0 <= t.kind < len(SELECT_KINDS) else None
+            if name == 'plane':
+                if len(values) != 1:
+                    raise ValueError('select_u8: a plane term takes one offset, got %r' % (term,))
+                t.plane_offset = values[0]
+            else:
+                if name in ('lum', 'sat', 'hue') and len(values) == 2:
+                    values = values + [0]
+                if len(values) > 4 or (name is not None and len(values) != (3 if name in ('lum', 'sat', 'hue') else 4)):
+                    raise ValueError('select_u8: wrong number of values in term %r' % (term,))
+                for k, v in enumerate(values):
+                    if not -2 ** 31 <= v < 2 ** 31:
+                        raise ValueError('select_u8: a value of term %r does not fit 32 bits' % (term,))
+                    t.p[k] = v
+    return arr
+
+
+def select_u8(src_u8, jobs, out=None):
+    """Mask planes from a rule in ONE launch (t2o_select_u8): job j = (src_offset, out_offset, h, w, terms) reads the uint8
+    (h, w, 3) RGB photo at byte src_offset of the 1-D uint8 GPU tensor src_u8 (any alignment; jobs may share a photo) and
+    writes the (h, w) uint8 plane of its selection at byte out_offset of `out` (allocated to fit when None).  terms: 1 to 4
+    integer terms as select_jobs takes them, multiplied left to right; a 'plane' term reads an (h, w) plane at its byte offset
+    in src_u8.  At most 4 jobs; no destination may overlap another one or, when out is src_u8, anything the call reads.
+    Every offset and size is checked here against the tensors, so that a wrong argument is a ValueError and never a GPU
+    fault.  Returns out (1-D uint8)."""
+    if not (torch.is_tensor(src_u8) and src_u8.is_cuda and src_u8.dtype == torch.uint8 and src_u8.is_contiguous()):
+        raise ValueError('select_u8: src must be a contiguous uint8 GPU tensor')
+    jobs = [tuple(j) for j in jobs]
+    if not 1 <= len(jobs) <= SELECT_MAX_JOBS:
+        raise ValueError('select_u8: 1 to 4 jobs per call, got %d' % len(jobs))
+    table = select_jobs(jobs)
+    live = [(j, c) for j, c in enumerate(table[:len(jobs)]) if c.h > 0 and c.w > 0]          # (an empty plane: the library refuses it)
+    for j, c in live:
+        if not (0 <= c.src_offset and c.src_offset + 3 * c.h * c.w <= src_u8.numel()):
+            raise ValueError('select_u8: job %d reads outside the %d-byte source' % (j, src_u8.numel()))
+        for t in c.terms[:min(c.n_terms, SELECT_MAX_TERMS)]:
+            if t.kind == SELECT_KINDS.index('plane') and not (0 <= t.plane_offset and t.plane_offset + c.h * c.w <= src_u8.numel()):
+                raise ValueError('select_u8: job %d reads a plane term outside the %d-byte source' % (j, src_u8.numel()))
+    for j, c in live:                                                                         # before `out` is allocated to fit
+        if c.out_offset < 0:
+            raise ValueError('select_u8: job %d writes before the output (out_offset %d)' % (j, c.out_offset))
+    need = max([c.out_offset + c.h * c.w for _, c in live] or [1])
+    if out is None:
+        out = torch.empty(need, dtype=torch.uint8, device=src_u8.device)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == src_u8.device):
+        raise ValueError('select_u8: out must be a contiguous uint8 GPU tensor on the source\'s device')
+    if out.numel() < need:
+        raise ValueError('select_u8: a job writes outside the %d-byte output' % out.numel())
+    rc = _lib.load().t2o_select_u8(_ptr(src_u8), _ptr(out), table, len(jobs), _stream(src_u8.device))
+    replay_status(rc, 't2o_select_u8')
+    return out
