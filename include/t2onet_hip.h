@@ -942,6 +942,48 @@ typedef struct {
 } t2o_select_job_t;
 int t2o_select_u8(const unsigned char* src, unsigned char* out, const t2o_select_job_t* jobs, int J, void* stream);
 
+/* ---- snapping the mask planes of a local edit to the photo's own edges on the device (t2o_refine.hip): the guided filter
+ * of He et al. with the photo's luminance as the guide, in INTEGER arithmetic.  Job j reads the (h,w,3) uint8 RGB photo
+ * at photo + photo_offset and the (h,w) uint8 plane at src + src_offset and writes (h,w) uint8 at out + out_offset (all
+ * three at any byte alignment; no byte outside the plane is written).  radius r in 0..64, eps2 = E in 1..65025 (the
+ * regulariser in byte^2 units).  All numbers are integers; // is FLOOR division (numerators can be negative):
+ *   I = (69 R + 172 G + 15 B + 128) >> 8                   the guide: t2o_select_u8's luminance L, 0..255
+ *   p = the plane's byte
+ *   box(v)(y, x) = sum of v[clamp(y+dy, 0, h-1), clamp(x+dx, 0, w-1)] over |dy|, |dx| <= r      replicated borders;
+ *                  n = (2r+1)^2 terms everywhere
+ *   S_I, S_p, S_II, S_Ip = box(I), box(p), box(I I), box(I p)          each <= 16641 * 65025 < 1.09e9: uint32
+ *   cov = n S_Ip - S_I S_p                                             signed 64-bit
+ *   var = n S_II - S_I^2 >= 0;  den = var + E n^2 > 0                  64-bit, den < 3.7e13
+ *   A = (2 * 1024 * cov + den) // (2 den)                              a in Q10, rounded half up; |A| <= 65281 as
+ *                                                                      |a| <= 63.75 / sqrt(E); |numerator| < 9.3e15
+ *   B = (2 (1024 S_p - A S_I) + n) // (2 n)                            |B| < 1.7e7: int32
+ *   T_A = box(A)   |T_A| <= 1.09e9: int32;     T_B = box(B)   64-bit (a row of 129 B's already passes 2^31)
+ *   out = clamp((2 (T_A I + T_B) + 1024 n) // (2 * 1024 * n), 0, 255)
+ * Exact consequences: a constant plane c comes out as c for any photo, r and E (cov = 0, A = 0, B = 1024 c); r = 0 is a
+ * copy; a constant photo gives A = 0 and a result that depends on the plane alone; flipping photo and plane in both axes
+ * flips the output.
+ * Four launches cover all jobs (row sums, column sums giving A and B, row sums, column sums giving the byte); every
+ * plane byte is read by the first and every destination byte written by the last, so a job may run in place
+ * (out + out_offset == src + src_offset) and a source may overlap any destination; photo may be the same buffer as src
+ * and out.  jobs: HOST array of 1 <= J <= 4, copied into the kernel arguments.  workspace: DEVICE, 16-byte aligned,
+ * t2o_refine_workspace_bytes (20 bytes per pixel with rows padded to 4 pixels; 0 for a job table that t2o_refine_u8
+ * would refuse).  No allocation, no host synchronisation, no float, no atomics; deterministic, capturable.  The caller
+ * guarantees that offsets and sizes lie inside photo / src / out.
+ * T2O_EINVAL, before any launch: null pointers, J outside 1..4, radius outside 0..64, eps2 outside 1..65025,
+ * non-positive sizes, h * w >= 2^31, negative offsets, a destination that overlaps (by address) another destination or
+ * a photo of the call.  T2O_EWORKSPACE: workspace null, too small or not 16-byte aligned. */
+#define T2O_REFINE_MAX_JOBS 4
+#define T2O_REFINE_MAX_RADIUS 64
+#define T2O_REFINE_MAX_EPS2 65025
+typedef struct {
+  long long photo_offset, src_offset, out_offset;   /* first byte of the photo / the plane / the destination, counted from photo / src / out */
+  int h, w;
+  int radius, eps2;
+} t2o_refine_job_t;
+size_t t2o_refine_workspace_bytes(const t2o_refine_job_t* jobs, int J);
+int t2o_refine_u8(const unsigned char* photo, const unsigned char* src, unsigned char* out, const t2o_refine_job_t* jobs, int J,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the metrics of the test loop in one call: utils/eval.py:50-60 (ImageEvaluator.update: input / output L1 and SSIM),
  * utils/ssim/__init__.py:20-40 (the SSIM itself) and test_seq2seqL1.py:60-74 (the END-image select and the two L1
  * distances the loop averages).  imgs: HOST array of 1 <= T <= 8 device pointers to (B,C,H,W) step images, first: device

@@ -20,6 +20,8 @@ of its own) is applied LOCALLY: a selection is a rule in units of the frame, so 
 own planes at its own size, computed on the device.  The photos are grouped so that a group names at most 4 planes; per
 group ONE functional.select_u8 launch writes the planes, functional.feather_u8's two launches soften them if asked, and
 ONE functional.replay_u8_any launch replays the list under them.  The new records carry 'select' and 'feather' along.
+A record that also has 'refine' (edit_cli --refine: {one of those names or 'all': [radius, eps]}) snaps each photo's planes
+to that photo's OWN luminance: functional.refine_u8's four launches run between the select launch and feather's two.
 Painted masks do not carry from photo to photo: a record with 'masks' and no 'select' is replayed globally, as before,
 and a record that has both is refused.
 """
@@ -86,10 +88,26 @@ def parse_local(record):
     return rules, sigmas
 
 
-def local_planes(ops, select, feather):
+def parse_refine(record):
+    """The 'refine' of a record with 'select' -> {one of the selections' names or 'all': (radius, eps)}, {} when it has none.
+    A record without 'select' is replayed globally, whatever else it holds.  Raises ValueError: a value that is not
+    [radius, eps], a name that no selection goes by."""
+    from .edit_cli import parse_refine_args
+    info = record[0] if isinstance(record, list) and record else record
+    refine = info.get('refine') if isinstance(info, dict) else None
+    if not refine or not isinstance(info.get('select'), dict):
+        return {}                                                     # (painted planes stay with their photo, and so does their refinement)
+    if not (isinstance(refine, dict) and all(isinstance(k, str) and isinstance(v, (list, tuple)) and len(v) == 2 for k, v in refine.items())):
+        raise ValueError('record: \'refine\' is {name: [radius, eps]}, got %r' % (refine,))
+    return parse_refine_args([('%s:%s' % tuple(v)) if name == 'all' else '%s=%s:%s' % (name, v[0], v[1]) for name, v in refine.items()],
+                             info['select'])
+
+
+def local_planes(ops, select, feather, refine=None):
     """Which planes a photo needs for `ops` under parse_local's (select, feather) -> ([(terms in user units, sigma)],
     mask_of): the distinct planes, and per step the plane's number or -1.  A named entry wins over 'all', in select and in
-    feather alike: an 'all' sigma stands for every plane that has none of its own (edit_cli.feather_argument)."""
+    feather alike: an 'all' sigma stands for every plane that has none of its own (edit_cli.feather_argument).  With
+    parse_refine's `refine` a plane is (terms, sigma, (radius, eps) or None), named entries winning in the same way."""
     from .edit_cli import parse_select_terms
     planes, mask_of = [], []
     for op in ops:
@@ -98,6 +116,9 @@ def local_planes(ops, select, feather):
             mask_of.append(-1)
             continue
         plane = (tuple(parse_select_terms(select[name])), float(feather.get(name, feather.get('all', 0.0))))
+        if refine is not None:
+            pair = refine.get(name, refine.get('all'))
+            plane += (tuple(pair) if pair is not None and pair[0] > 0 else None,)
         if plane not in planes:
             planes.append(plane)
         mask_of.append(planes.index(plane))
@@ -106,13 +127,16 @@ def local_planes(ops, select, feather):
     return planes, mask_of
 
 
-def apply_record_local(images, ops, params, select, feather, multi_img=False, device=None):
+def apply_record_local(images, ops, params, select, feather, multi_img=False, device=None, refine=None):
     """apply_record under the selections of parse_local: the same result layout.  One upload; per group of photos that
-    together name at most 4 planes: one select_u8 launch, feather_u8 where a sigma is given, one replay launch."""
+    together name at most 4 planes: one select_u8 launch, refine_u8's four where parse_refine's `refine` gives a radius,
+    feather_u8 where a sigma is given, one replay launch."""
     from . import functional as T
-    from .edit import select_terms
+    from .edit import refine_eps2, select_terms
     assert (MAX_STEPS, MAX_JOBS, PARAM_PAD, MAX_PLANES) == (T.REPLAY_MAX_STEPS, T.REPLAY_MAX_JOBS, T.PARAM_PAD, T.REPLAY_MAX_MASKS)
-    planes, mask_of = local_planes(ops, select, feather)
+    planes, mask_of = local_planes(ops, select, feather, refine or None)
+    snaps = [(p[2][0], refine_eps2(p[2][1])) if len(p) == 3 and p[2] else None for p in planes]      # before any device use
+    planes = [p[:2] for p in planes]
     if not planes:                                                    # no operation of the list is selected for
         return apply_record(images, ops, params, multi_img, device)
     shapes = [tuple(int(v) for v in im.shape[:2]) for im in images]
@@ -130,12 +154,14 @@ def apply_record_local(images, ops, params, select, feather, multi_img=False, de
     per = MAX_PLANES // len(planes)                                   # photos of a group
     for a in range(0, len(images), per):
         group = list(range(a, min(a + per, len(images))))
-        sel_jobs, soft_jobs, jobs, where, at, pos = [], [], [], {}, 0, 0
+        sel_jobs, snap_jobs, soft_jobs, jobs, where, at, pos = [], [], [], [], {}, 0, 0
         for i in group:
             h, w = shapes[i]
             for k, (_, sigma) in enumerate(planes):
                 where[i, k] = len(sel_jobs)
                 sel_jobs.append((offsets[i], at, h, w, rules[i][k]))
+                if snaps[k]:
+                    snap_jobs.append((offsets[i], at, at, h, w) + snaps[k])
                 if sigma > 0.0:
                     soft_jobs.append((at, at, h, w, sigma))
                 at += h * w
@@ -143,6 +169,8 @@ def apply_record_local(images, ops, params, select, feather, multi_img=False, de
                 jobs.append((offsets[i], pos, h, w, list(ops[:n]), [where[i, k] if k >= 0 else -1 for k in mask_of[:n]]))
                 pos += 3 * h * w
         plane_buffer = T.select_u8(dev_buffer, sel_jobs)
+        if snap_jobs:
+            T.refine_u8(dev_buffer, plane_buffer, snap_jobs)
         if soft_jobs:
             T.feather_u8(plane_buffer, soft_jobs)
         out = T.replay_u8_any(dev_buffer, jobs, row.unsqueeze(0).expand(len(jobs), -1, -1).contiguous(), plane_buffer,
@@ -212,14 +240,17 @@ def main(argv=None):
         record = json.load(f)
     request, ops, params = parse_record(record)                       # before any decode or device use
     local = parse_local(record)
+    refine = parse_refine(record)
     images = [decode_image(p) for p in args.img]
     from .edit_cli import write_outputs
     infos = []
     if local is None:
         results, carried = apply_record(images, ops, params, args.multi_img), {}
     else:
-        results = apply_record_local(images, ops, params, local[0], local[1], args.multi_img)
+        results = apply_record_local(images, ops, params, local[0], local[1], args.multi_img, refine=refine)
         carried = {'select': local[0], 'feather': local[1] or None}
+        if refine:
+            carried['refine'] = refine
     for path, img, steps in zip(args.img, images, results):
         info = write_outputs(args.save_dir, path, request, img, steps, ops, params, args.multi_img, **carried)
         info['record'] = args.record

@@ -80,6 +80,53 @@ def checked_feather(feather, masks):
     return {plane: sigma for plane, sigma in by_plane.items() if sigma > 0.0}
 
 
+def refine_eps2(eps):
+    """The regulariser of a refinement, a fraction of full scale in (0, 1], in the byte^2 units of functional.refine_u8:
+    E = max(1, floor((255 eps)^2 + 0.5)) in double."""
+    eps = float(eps)
+    if not 0.0 < eps <= 1.0:
+        raise ValueError('edit_image: refine eps = %r, a fraction of full scale in (0, 1]' % (eps,))
+    return max(1, int(np.floor((np.float64(255.0) * np.float64(eps)) ** 2 + 0.5)))
+
+
+REFINE_EPS = 0.02
+
+
+def _refine_value(key, value):
+    """A refinement as given -- a radius or (radius, eps) -- -> (radius, E)."""
+    pair = tuple(value) if isinstance(value, (tuple, list)) else (value,)
+    if not 1 <= len(pair) <= 2:
+        raise ValueError('edit_image: refine %r = %r is neither a radius nor (radius, eps)' % (key, value))
+    try:
+        radius, eps = float(pair[0]), float(pair[1] if len(pair) == 2 else REFINE_EPS)
+    except (TypeError, ValueError):
+        raise ValueError('edit_image: refine %r = %r has a value that is not a number' % (key, value))
+    if not (radius == int(radius) and 0 <= radius <= T.REFINE_MAX_RADIUS):
+        raise ValueError('edit_image: refine %r = %r, a radius is a whole number of pixels in 0..%d' % (key, value, T.REFINE_MAX_RADIUS))
+    return int(radius), refine_eps2(eps)
+
+
+def checked_refine(refine, masks):
+    """refine (None, a radius, (radius, eps), or {key of masks: either}) -> {id of the mask object: (radius > 0, E)}.  eps is
+    a fraction of full scale in (0, 1] (REFINE_EPS when left out; refine_eps2 gives E).  Two keys that name one plane must
+    agree; a radius of 0 leaves its plane as it is."""
+    if refine is None:
+        return {}
+    if masks is None:
+        raise ValueError('edit_image: refine without masks -- there is no plane to refine')
+    if not isinstance(refine, dict):
+        refine = {key: refine for key in masks}
+    by_plane = {}
+    for key, value in refine.items():
+        if key not in masks:
+            raise ValueError('edit_image: refine key %r names no mask (masks: %s)' % (key, ', '.join(repr(k) for k in masks)))
+        pair = _refine_value(key, value)
+        if by_plane.setdefault(id(masks[key]), pair) != pair:
+            raise ValueError('edit_image: refine %r = %r, but another key refines the same plane by %r'
+                             % (key, pair, by_plane[id(masks[key])]))
+    return {plane: pair for plane, pair in by_plane.items() if pair[0] > 0}
+
+
 def _round_unit(v, scale):
     """floor(v * scale + 0.5) in double: the host rounding of a selection's user units."""
     return int(np.floor(np.float64(v) * np.float64(scale) + 0.5))
@@ -165,13 +212,14 @@ def _key_targets(key, what):
     raise ValueError('edit_image: %s key %r is neither \'all\' nor an executor operator index 0..7' % (what, key))
 
 
-def select_plan(select, masks, feather, h, w):
+def select_plan(select, masks, feather, h, w, refine=None):
     """The planes of an edit_image call that gives `select` -- checked without any device use.  select: {executor operator
     index or 'all': selection in user units}, keyed like masks.  Every key of select or masks gets a plane: its selection,
     multiplied by its painted mask when the SAME key has one (a 'plane' term: the intersection); a key with only a painted
     mask is a one-term 'plane' job.  Keys whose rule and painted plane agree share a plane.  Returns (painted, specs, by_op,
     sigma_of): the distinct painted planes to upload, per plane (integer terms, number of its painted plane or None),
-    {operator index: plane number} ('all' first, an entry for one operator wins), {plane number: sigma > 0}."""
+    {operator index: plane number} ('all' first, an entry for one operator wins), {plane number: sigma > 0}.  With `refine`
+    (keyed like feather; checked_refine) a fifth value follows: {plane number: (radius > 0, E)}."""
     if not isinstance(select, dict) or not select:
         raise ValueError('edit_image: select is {executor operator index or \'all\': [terms]}')
     masks = masks or {}
@@ -202,7 +250,10 @@ def select_plan(select, masks, feather, h, w):
     handles = [object() for _ in specs]                               # checked_feather tells planes apart by identity
     by_handle = checked_feather(feather, {key: handles[no] for key, no in tokens.items()})
     sigma_of = {no: by_handle[id(hd)] for no, hd in enumerate(handles) if id(hd) in by_handle}
-    return painted, specs, by_op, sigma_of
+    if refine is None:
+        return painted, specs, by_op, sigma_of
+    by_handle = checked_refine(refine, {key: handles[no] for key, no in tokens.items()})
+    return painted, specs, by_op, sigma_of, {no: by_handle[id(hd)] for no, hd in enumerate(handles) if id(hd) in by_handle}
 
 
 def _append_planes(buffer, planes):
@@ -228,7 +279,7 @@ def _proxy_mask_dict(dev_buffer, mask_offsets, by_op, size, proxy_size):
     return [{str(op + 3): [proxies[slot]] for op, slot in by_op.items()}]
 
 
-def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, select=None):
+def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, select=None, refine=None):
     """img_u8_hwc: the decoded photo, uint8 (h,w,3) RGB (array or CPU tensor); x: (1, L) request token ids.
     Returns (steps_u8, ops, params):
       steps_u8  (max(n,1), h, w, 3) uint8 GPU tensor: picture k is the photo after the first k+1 of the n chosen operators,
@@ -256,16 +307,23 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, 
     frame) and are written on the device by ONE functional.select_u8 launch into one tensor, which feather, the proxy and
     the replay then read as they read the uploaded planes.  A key that also has a painted mask gets the product of the two
     (the intersection); a key with only a painted mask keeps it; feather may name either.  Nothing but the photo (and the
-    painted planes) is uploaded.  Wrong specifications raise ValueError before any device use (select_plan)."""
+    painted planes) is uploaded.  Wrong specifications raise ValueError before any device use (select_plan).
+    refine: None, a radius in pixels of the photo (every plane), (radius, eps), or {key of masks / select: either} -- the
+    planes are snapped to the photo's own edges by functional.refine_u8's exact integer guided filter (guide = the photo's
+    luminance; eps, a fraction of full scale in (0, 1], default 0.02, is how much contrast counts as an edge) IN PLACE in
+    the buffer the later stages read: after select, before feather, the proxy's mask_dict and the replay, so that the
+    proxy's decision and the native replay see the same plane.  Four launches, whatever the number of planes.  Keys that
+    share one plane must agree; refine without masks or select is an error; None is the path without it, launch for launch."""
     img = T._u8_hwc(img_u8_hwc)
     h, w = img.shape[:2]
-    plan = select_plan(select, masks, feather, h, w) if select is not None else None       # before any device use
+    plan = select_plan(select, masks, feather, h, w, refine if refine is not None else {}) if select is not None else None    # before any device use
     sigma_of = checked_feather(feather, masks) if plan is None else {}                       # before any device use
+    refine_of = checked_refine(refine, masks) if plan is None else {}                        # before any device use
     dev = next(model.parameters()).device
     opt = model.opt
     slot_of = {}
     if plan is not None:
-        planes, specs, by_op, plane_sigma = plan
+        planes, specs, by_op, plane_sigma, plane_refine = plan
     else:
         planes, by_op = _checked_masks(masks, h, w, slot_of) if masks is not None else ([], {})
     local = masks is not None or plan is not None
@@ -281,10 +339,15 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, 
                 for k, (terms, slot) in enumerate(specs)]
         mask_buffer = T.select_u8(dev_buffer, jobs)
         mask_offsets = [k * h * w for k in range(len(specs))]
+        if plane_refine:
+            T.refine_u8(dev_buffer, mask_buffer, [(int(descs[0]['offset']),) + (mask_offsets[k],) * 2 + (h, w, r, E) for k, (r, E) in plane_refine.items()])
         if plane_sigma:
             T.feather_u8(mask_buffer, [(mask_offsets[k],) * 2 + (h, w, sigma) for k, sigma in plane_sigma.items()])
-    elif sigma_of:
-        T.feather_u8(dev_buffer, [(mask_offsets[slot_of[p]],) * 2 + (h, w, sigma) for p, sigma in sigma_of.items()])
+    else:
+        if refine_of:
+            T.refine_u8(dev_buffer, dev_buffer, [(int(descs[0]['offset']),) + (mask_offsets[slot_of[p]],) * 2 + (h, w, r, E) for p, (r, E) in refine_of.items()])
+        if sigma_of:
+            T.feather_u8(dev_buffer, [(mask_offsets[slot_of[p]],) * 2 + (h, w, sigma) for p, sigma in sigma_of.items()])
     ph, pw = short_side_size(h, w, proxy_short) if min(h, w) > proxy_short else (h, w)
     proxy = T._resize_launch(dev_buffer, table_ptr, 1, ph, pw)
     mask_dict = _proxy_mask_dict(mask_buffer, mask_offsets, by_op, (h, w), (ph, pw)) if local else None

@@ -24,6 +24,12 @@ of the short side); a leading '!' inverts a term, '+' multiplies terms (at most 
 and a --mask under the same name are intersected; --feather NAME= may name a --select as well.  The record then also
 holds 'select': {name or 'all': the terms as given}, which apply_cli replays on other photos of any size.
 
+--refine [NAME=]RADIUS[:EPS] (repeatable) snaps a plane to the photo's own edges on the device before it is feathered and
+used: the exact integer guided filter of edit.edit_image's `refine`, guided by the photo's luminance, over a window of
+RADIUS pixels (a whole number, at most 64); EPS, a fraction of full scale in (0, 1] (default 0.02), is how much contrast
+counts as an edge.  NAME is a name a --mask or --select was given under; without a name every plane is refined.  The
+record then also holds 'refine': {name or 'all': [radius, eps]}, which apply_cli replays under each photo's own luminance.
+
 The actor decides on a proxy of the photo (short side --proxy_short, the test loader's 600; a smaller photo is its own
 proxy) and the decision is applied to the photo at its native size by the fused 8-bit replay kernel (edit.edit_image).
 
@@ -93,6 +99,51 @@ def parse_feather_args(specs, named):
             raise ValueError('--feather %s: SIGMA must lie in [0, 64]' % spec)
         sigmas[name] = sigma
     return sigmas
+
+
+def parse_refine_args(specs, named):
+    """--refine values ([NAME=]RADIUS[:EPS]) -> {name or 'all': (radius, eps)}; named: every name a plane goes by.  NAME
+    must be one of them, RADIUS a whole number in 0..64, EPS a number in (0, 1] (0.02 when left out); no NAME means every
+    plane.  Raises ValueError naming the spec."""
+    import math
+    from .edit import REFINE_EPS
+    refines = {}
+    for spec in specs or []:
+        head, sep, tail = spec.partition('=')
+        name, text = (head, tail) if sep else ('all', spec)
+        if not named:
+            raise ValueError('--refine %s: there is no --mask or --select to refine' % spec)
+        if sep and name not in named:
+            raise ValueError('--refine %s: no --mask or --select was given under %r (given: %s)' % (spec, name, ', '.join(sorted(named))))
+        fields = text.split(':')
+        if len(fields) not in (1, 2) or not fields[0]:
+            raise ValueError('--refine %s: expected RADIUS[:EPS]' % spec)
+        try:
+            radius = int(fields[0])
+        except ValueError:
+            raise ValueError('--refine %s: RADIUS %r is not a whole number' % (spec, fields[0]))
+        if not 0 <= radius <= 64:
+            raise ValueError('--refine %s: RADIUS must lie in 0..64' % spec)
+        try:
+            eps = float(fields[1]) if len(fields) == 2 else REFINE_EPS
+        except ValueError:
+            raise ValueError('--refine %s: EPS %r is not a number' % (spec, fields[1]))
+        if math.isnan(eps) or not 0.0 < eps <= 1.0:
+            raise ValueError('--refine %s: EPS must lie in (0, 1]' % spec)
+        refines[name] = (radius, eps)
+    return refines
+
+
+def refine_argument(refines, named):
+    """{name or 'all': (radius, eps)} of parse_refine_args -> the `refine` argument of edit.edit_image, keyed like the planes
+    of `named`.  An unnamed value stands for every plane; a named one wins over it (as feather_argument)."""
+    if not refines:
+        return None
+    refine = {}
+    for name in named:
+        if name in refines or 'all' in refines:
+            refine['all' if name == 'all' else ACTIONS.index(name)] = tuple(refines.get(name, refines.get('all')))
+    return refine
 
 
 def parse_select_terms(spec):
@@ -174,9 +225,11 @@ def load_masks(named, h, w):
     return masks
 
 
-def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, multi_img=False, masks=None, feather=None, select=None):
+def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, multi_img=False, masks=None, feather=None, select=None,
+                  refine=None):
     """The files of one edit (see the module docstring); steps_u8: (max(n,1), h, w, 3) uint8 array; masks: {name: file}
-    of a local edit, feather: {name: sigma} and select: {name: terms as given}, each recorded when given.  Returns the record."""
+    of a local edit, feather: {name: sigma}, select: {name: terms as given} and refine: {name: (radius, eps)}, each recorded
+    when given.  Returns the record."""
     from PIL import Image
     name, ext = os.path.splitext(os.path.basename(img_path))
     out_dir = os.path.join(save_dir, name)
@@ -194,6 +247,8 @@ def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, mu
         info['feather'] = dict(feather)
     if select:
         info['select'] = dict(select)
+    if refine:
+        info['refine'] = {name: [int(v[0]), float(v[1])] for name, v in refine.items()}
     with open(os.path.join(out_dir, name + '.json'), 'w') as f:
         json.dump([info], f)
     return info
@@ -218,21 +273,28 @@ def main(argv=None):
     ap.add_argument('--select', action='append', default=None, metavar='[NAME=]TERM[+TERM...]',
                     help='a local edit by a rule instead of a mask file: lum:LO:HI[:SOFT], sat:LO:HI[:SOFT], hue:LO:HI[:SOFT], '
                          'linear:X0,Y0:X1,Y1, radial:CX,CY:RIN:ROUT, ! in front inverts, + multiplies; NAME as for --mask; repeatable')
+    ap.add_argument('--refine', action='append', default=None, metavar='[NAME=]RADIUS[:EPS]',
+                    help='snap a plane to the photo\'s own edges on the device (guided filter, window RADIUS <= 64 pixels, EPS in '
+                         '(0, 1], default 0.02) before it is feathered and used; NAME = a name a --mask or --select was given '
+                         'under, without it every plane; repeatable')
     args = ap.parse_args(argv)
     named = parse_mask_args(args.mask)
     rules = parse_select_args(args.select)
     planes = dict(named, **rules)                                                  # every name a plane goes by
     sigmas = parse_feather_args(args.feather, planes)                              # before the model: a wrong value fails early
+    refines = parse_refine_args(args.refine, planes)
     img = decode_image(args.img)
     masks = load_masks(named, img.shape[0], img.shape[1]) if named else None       # before the model: a wrong mask fails early
     feather = feather_argument(sigmas, planes)
     select = select_argument(rules)
+    refine = refine_argument(refines, planes)
     if select:
         from .edit import select_plan
-        select_plan(select, masks, feather, img.shape[0], img.shape[1])            # a gradient that collapses on this photo, too many planes
-    elif feather:
-        from .edit import checked_feather
+        select_plan(select, masks, feather, img.shape[0], img.shape[1], refine)    # a gradient that collapses on this photo, too many planes
+    else:
+        from .edit import checked_feather, checked_refine
         checked_feather(feather, masks)                                            # two names, one file, two sigmas
+        checked_refine(refine, masks)
 
     from . import default_options
     from .actor import Actor
@@ -244,9 +306,9 @@ def main(argv=None):
     model.load_state_dict(torch.load(args.checkpoint, map_location='cpu'), strict=False)      # as the demo (:129)
     model.to(device)
     steps_u8, ops, params = edit_image(model, img, request_to_idx(args.request, vocab2id, opt), args.proxy_short, masks=masks,
-                                      feather=feather, select=select)
+                                      feather=feather, select=select, **({'refine': refine} if refine else {}))
     info = write_outputs(args.save_dir, args.img, args.request, img, steps_u8.cpu().numpy(), ops, params.cpu(), args.multi_img,
-                         masks=named or None, feather=sigmas or None, select=rules or None)
+                         masks=named or None, feather=sigmas or None, select=rules or None, refine=refines or None)
     print('%s: %s -> %s' % (args.request, ', '.join(n for n, _ in info['operations']) or '(no operator)',
                             os.path.join(args.save_dir, os.path.splitext(os.path.basename(args.img))[0], info['output'])))
     return info

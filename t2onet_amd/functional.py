@@ -2471,3 +2471,79 @@ def select_u8(src_u8, jobs, out=None):
     rc = _lib.load().t2o_select_u8(_ptr(src_u8), _ptr(out), table, len(jobs), _stream(src_u8.device))
     replay_status(rc, 't2o_select_u8')
     return out
+
+
+# ---- mask refinement (t2o_refine.hip): a plane snapped to the photo's own edges, the guided filter in exact integers ----
+
+REFINE_MAX_JOBS, REFINE_MAX_RADIUS, REFINE_MAX_EPS2, REFINE_LAUNCHES = 4, 64, 65025, 4
+
+
+class RefineJob(ctypes.Structure):
+    """t2o_refine_job_t of include/t2onet_hip.h (field for field)."""
+    _fields_ = [('photo_offset', ctypes.c_longlong), ('src_offset', ctypes.c_longlong), ('out_offset', ctypes.c_longlong),
+                ('h', ctypes.c_int), ('w', ctypes.c_int), ('radius', ctypes.c_int), ('eps2', ctypes.c_int)]
+
+
+def refine_jobs(jobs):
+    """jobs: a sequence of (photo_offset, src_offset, out_offset, h, w, radius, eps2) -> the ctypes array t2o_refine_u8
+    takes.  Integers only; a value that does not fit its field is a ValueError."""
+    arr = (RefineJob * max(len(jobs), 1))()
+    for c, job in zip(arr, jobs):
+        if len(job) != 7:
+            raise ValueError('refine_u8: a job is (photo_offset, src_offset, out_offset, h, w, radius, eps2), got %r' % (job,))
+        values = [int(v) for v in job]
+        if any(v != f for v, f in zip(values, job)):
+            raise ValueError('refine_u8: job %r holds a value that is not an integer' % (job,))
+        if not all(-2 ** 63 <= v < 2 ** 63 for v in values[:3]) or not all(-2 ** 31 <= v < 2 ** 31 for v in values[3:]):
+            raise ValueError('refine_u8: a value of job %r does not fit its field' % (job,))
+        c.photo_offset, c.src_offset, c.out_offset, c.h, c.w, c.radius, c.eps2 = values
+    return arr
+
+
+_refine_ws = {}
+
+
+def _refine_workspace(need, device):
+    """The intermediates of refine_u8: cached per device and stream like _feather_workspace, a buffer of its own -- 20 bytes
+    per pixel of every plane of the call."""
+    return _scratch(need, device, _refine_ws, 16)
+
+
+def refine_u8(photo_u8, buffer, jobs, out=None):
+    """Snap uint8 planes to the edges of their photo on the device in FOUR launches, whatever their number
+    (t2o_refine_u8): job j = (photo_offset, src_offset, out_offset, h, w, radius, eps2) runs the exact integer guided filter
+    of include/t2onet_hip.h -- guide = the luminance of the (h, w, 3) uint8 RGB photo at byte photo_offset of the 1-D uint8 GPU
+    tensor photo_u8, window radius <= 64, regulariser eps2 in 1..65025 (byte^2) -- on the (h, w) plane at byte src_offset of
+    the 1-D uint8 GPU tensor `buffer` and writes it at byte out_offset of `out` -- of `buffer` itself when out is None: in
+    place where the two offsets agree.  Any byte alignment; photo_u8 may be `buffer`.  At most 4 jobs; a destination may not
+    overlap another one or a photo of the call, a source may overlap any destination.  Every offset and size is checked here
+    against the tensors, so that a wrong argument is a ValueError and never a GPU fault.  Returns out."""
+    def ok(t):
+        return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    if not (ok(photo_u8) and ok(buffer)) or photo_u8.device != buffer.device:
+        raise ValueError('refine_u8: photo and buffer must be contiguous uint8 GPU tensors on one device')
+    if out is None:
+        out = buffer
+    elif not (ok(out) and out.device == buffer.device):
+        raise ValueError('refine_u8: out must be a contiguous uint8 GPU tensor on the buffer\'s device')
+    jobs = [tuple(j) for j in jobs]
+    if not 1 <= len(jobs) <= REFINE_MAX_JOBS:
+        raise ValueError('refine_u8: 1 to 4 jobs per call, got %d' % len(jobs))
+    table = refine_jobs(jobs)
+    for j, c in enumerate(table[:len(jobs)]):
+        if c.out_offset < 0:                                     # before anything is allocated
+            raise ValueError('refine_u8: job %d writes before the output (out_offset %d)' % (j, c.out_offset))
+        if not (c.h > 0 and c.w > 0):
+            continue                                             # the library refuses it
+        if not (0 <= c.photo_offset and c.photo_offset + 3 * c.h * c.w <= photo_u8.numel()):
+            raise ValueError('refine_u8: job %d reads outside the %d-byte photo buffer' % (j, photo_u8.numel()))
+        if not (0 <= c.src_offset and c.src_offset + c.h * c.w <= buffer.numel()):
+            raise ValueError('refine_u8: job %d reads outside the %d-byte buffer' % (j, buffer.numel()))
+        if not c.out_offset + c.h * c.w <= out.numel():
+            raise ValueError('refine_u8: job %d writes outside the %d-byte output' % (j, out.numel()))
+    lib = _lib.load()
+    need = lib.t2o_refine_workspace_bytes(table, len(jobs))      # 0 for a table the library refuses: it says why below
+    ws = _refine_workspace(need, buffer.device)
+    rc = lib.t2o_refine_u8(_ptr(photo_u8), _ptr(buffer), _ptr(out), table, len(jobs), _ptr(ws), ws.numel(), _stream(buffer.device))
+    replay_status(rc, 't2o_refine_u8')
+    return out
