@@ -984,6 +984,47 @@ size_t t2o_refine_workspace_bytes(const t2o_refine_job_t* jobs, int J);
 int t2o_refine_u8(const unsigned char* photo, const unsigned char* src, unsigned char* out, const t2o_refine_job_t* jobs, int J,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the magic wand of a local edit on the device (t2o_region.hip): the CONNECTED region around a seed pixel, by
+ * union-find labelling.  Job j reads the (h,w,3) uint8 RGB photo at photo + photo_offset and writes the (h,w) uint8 plane
+ * at out + out_offset (both at any byte alignment; no byte outside the plane is written).  Integers only:
+ *   (Rs, Gs, Bs) = the photo's bytes at the seed pixel (seed_x, seed_y), READ ON THE DEVICE (no host read)
+ *   pass(y, x) <=> max(|R - Rs|, |G - Gs|, |B - Bs|) <= tol                  tol in 0..255; the seed always passes
+ *   out(y, x)  =  255 where (y, x) is joined to the seed by a path of passing pixels, else 0
+ *                 conn = 4: steps of the path are horizontal or vertical;  conn = 8: diagonal steps too
+ * A hard 0/255 plane; t2o_refine_u8 and t2o_feather_u8 soften it.
+ * THREE launches cover all jobs, whatever the pictures hold.  The parent array L (int32 per pixel, index i = y w + x) has
+ * L[i] < 0 for a pixel that does not pass, L[i] = i for a root and L[i] <= i always.  (1) a workgroup labels a 64 x 64 tile
+ * in LDS (runs along rows, min-index unions with the row above) and writes each pixel's parent as the global index of its
+ * tile-local root; (2) the pixels of a tile's top row and left column are joined with their passing neighbours across the
+ * tile edge: find both roots, atomicMin the larger root's word to the smaller, continue with the returned value where the
+ * word was no root any more; (3) one lane per workgroup finds the seed's root, every lane the roots of four neighbouring
+ * pixels, and stores one aligned dword (single bytes at the two ends of a misaligned plane).
+ * Visibility: in (2) and (3) every access to L is an agent-scope relaxed atomic (served by L2, never by a CU's L1); (1)
+ * uses plain stores, which the kernel boundary publishes.
+ * Progress: no workgroup waits for another -- no flag, spin, hand-off or grid barrier.  find follows strictly falling
+ * indices (every value word i ever holds is <= i, so a stale value cannot lengthen it); a union retries only with an index
+ * strictly below the one it held; path compression lowers a word to an ancestor, by atomicMin only.  So L[i] <= i and
+ * "same component" are never broken, and a defect could give wrong bytes but never a hang.
+ * A root is the smallest index of its component whatever the order of arrival: the output bytes AND the final roots are
+ * deterministic (the other words of L are not).
+ * photo and out may be one buffer.  jobs: HOST array of 1 <= J <= 4, copied into the kernel arguments; jobs may share a
+ * photo.  workspace: DEVICE, 16-byte aligned, t2o_region_workspace_bytes = the sum over the jobs of 4 h w rounded up to a
+ * multiple of 16 (0 for a job table that t2o_region_u8 would refuse).  No allocation, no host synchronisation, no float;
+ * capturable.  The caller guarantees that offsets and sizes lie inside photo / out.
+ * T2O_EINVAL, before any launch: null pointers, J outside 1..4, non-positive sizes, h * w >= 2^31, negative offsets, a
+ * seed outside the frame, tol outside 0..255, conn other than 4 or 8, a destination that overlaps (by address) another
+ * destination or a photo of the call.  T2O_EWORKSPACE: workspace null, too small or not 16-byte aligned. */
+#define T2O_REGION_MAX_JOBS 4
+typedef struct {
+  long long photo_offset, out_offset;  /* first byte of the photo / the destination, counted from photo / out */
+  int h, w;
+  int seed_x, seed_y;
+  int tol, conn;                       /* 0..255; 4 or 8 */
+} t2o_region_job_t;
+size_t t2o_region_workspace_bytes(const t2o_region_job_t* jobs, int J);
+int t2o_region_u8(const unsigned char* photo, unsigned char* out, const t2o_region_job_t* jobs, int J,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the metrics of the test loop in one call: utils/eval.py:50-60 (ImageEvaluator.update: input / output L1 and SSIM),
  * utils/ssim/__init__.py:20-40 (the SSIM itself) and test_seq2seqL1.py:60-74 (the END-image select and the two L1
  * distances the loop averages).  imgs: HOST array of 1 <= T <= 8 device pointers to (B,C,H,W) step images, first: device

@@ -18,7 +18,8 @@ A record with 'select' (edit_cli --select: {operator name or 'all': TERM[+TERM..
 those names: sigma in pixels}; as in edit_cli, 'all' is the unnamed --feather and softens every plane that has no sigma
 of its own) is applied LOCALLY: a selection is a rule in units of the frame, so every photo gets its
 own planes at its own size, computed on the device.  The photos are grouped so that a group names at most 4 planes; per
-group ONE functional.select_u8 launch writes the planes, functional.feather_u8's two launches soften them if asked, and
+group functional.region_u8 labels the connected regions of its 'wand' terms (each photo from its own seed pixel), ONE
+functional.select_u8 launch writes the planes, functional.feather_u8's two launches soften them if asked, and
 ONE functional.replay_u8_any launch replays the list under them.  The new records carry 'select' and 'feather' along.
 A record that also has 'refine' (edit_cli --refine: {one of those names or 'all': [radius, eps]}) snaps each photo's planes
 to that photo's OWN luminance: functional.refine_u8's four launches run between the select launch and feather's two.
@@ -130,9 +131,13 @@ def local_planes(ops, select, feather, refine=None):
 def apply_record_local(images, ops, params, select, feather, multi_img=False, device=None, refine=None):
     """apply_record under the selections of parse_local: the same result layout.  One upload; per group of photos that
     together name at most 4 planes: one select_u8 launch, refine_u8's four where parse_refine's `refine` gives a radius,
-    feather_u8 where a sigma is given, one replay launch."""
+    feather_u8 where a sigma is given, one replay launch.  A 'wand' / 'wand8' term is resolved per photo at that photo's
+    size: its seed pixel from the fractions of the rule, one functional.region_u8 job per distinct (seed, tolerance,
+    connectivity) of the photo, in calls of at most 4 in front of the group's select launch; the region planes lie in room
+    reserved on the device behind the uploaded buffer (no byte is uploaded for it), where the select launch reads them as
+    'plane' terms."""
     from . import functional as T
-    from .edit import refine_eps2, select_terms
+    from .edit import refine_eps2, select_terms, upload_with_room, wand_keys, wand_resolved
     assert (MAX_STEPS, MAX_JOBS, PARAM_PAD, MAX_PLANES) == (T.REPLAY_MAX_STEPS, T.REPLAY_MAX_JOBS, T.PARAM_PAD, T.REPLAY_MAX_MASKS)
     planes, mask_of = local_planes(ops, select, feather, refine or None)
     snaps = [(p[2][0], refine_eps2(p[2][1])) if len(p) == 3 and p[2] else None for p in planes]      # before any device use
@@ -144,7 +149,16 @@ def apply_record_local(images, ops, params, select, feather, multi_img=False, de
     if device is None:
         device = torch.device('cuda', torch.cuda.current_device())
     buffer, descs = T.pack_u8(images)
-    dev_buffer, _, descs, _keep = T.upload_packed(buffer, descs, device)
+    wands = [wand_keys(r) for r in rules]                             # per photo: its own seed pixels
+    if any(wands):
+        wand_at, pos = [], buffer.numel()
+        for (h, w), keys in zip(shapes, wands):
+            wand_at.append({key: pos + k * h * w for k, key in enumerate(keys)})
+            pos += len(keys) * h * w
+        dev_buffer, _, descs, _keep = upload_with_room(buffer, descs, pos - buffer.numel(), device)
+        rules = [[wand_resolved(terms, at) for terms in r] for r, at in zip(rules, wand_at)]
+    else:
+        dev_buffer, _, descs, _keep = T.upload_packed(buffer, descs, device)
     offsets = [int(d['offset']) for d in descs]
     row = torch.zeros(MAX_STEPS, PARAM_PAD)
     row[:len(ops)] = torch.as_tensor(np.asarray(params, np.float32).reshape(len(ops), PARAM_PAD))
@@ -168,6 +182,9 @@ def apply_record_local(images, ops, params, select, feather, multi_img=False, de
             for n in prefixes:
                 jobs.append((offsets[i], pos, h, w, list(ops[:n]), [where[i, k] if k >= 0 else -1 for k in mask_of[:n]]))
                 pos += 3 * h * w
+        wand_jobs = [(offsets[i], wand_at[i][key]) + shapes[i] + key for i in group for key in wands[i]]
+        for k in range(0, len(wand_jobs), T.REGION_MAX_JOBS):
+            T.region_u8(dev_buffer, wand_jobs[k:k + T.REGION_MAX_JOBS], out=dev_buffer)
         plane_buffer = T.select_u8(dev_buffer, sel_jobs)
         if snap_jobs:
             T.refine_u8(dev_buffer, plane_buffer, snap_jobs)

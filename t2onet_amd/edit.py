@@ -148,7 +148,9 @@ def check_select_terms(terms, who='edit_image'):
     """The checks of a selection in user units that do not need the photo's size; raises ValueError naming the term.
     terms: 1 to 4 of ('[!]lum' | '[!]sat', lo, hi[, soft]) in fractions [0, 1], ('[!]hue', lo, hi[, soft]) in degrees
     [0, 360) with soft <= 180, ('[!]linear', x0, y0, x1, y1) in fractions of w - 1 / h - 1, ('[!]radial', cx, cy, rin, rout)
-    with the radii in fractions of min(h, w); a leading '!' inverts the term."""
+    with the radii in fractions of min(h, w), ('[!]wand' | '[!]wand8', x, y[, tol]) -- the 4- / 8-connected region around the
+    seed at fractions x, y of w - 1 / h - 1, which must lie IN [0, 1] (inside the frame), of the pixels whose bytes differ
+    from the seed's by at most the fraction tol in [0, 1] of 255 (WAND_TOL when left out); a leading '!' inverts the term."""
     terms = list(terms) if isinstance(terms, (tuple, list)) else None
     if not terms or len(terms) > T.SELECT_MAX_TERMS:
         raise ValueError('%s: a selection is a list of 1 to %d terms' % (who, T.SELECT_MAX_TERMS))
@@ -172,15 +174,59 @@ def check_select_terms(terms, who='edit_image'):
                 raise ValueError('%s: select term %r: the two end points are equal' % (who, term))
             if kind == 'radial' and not 0.0 <= v[2] < v[3] <= 2.0:
                 raise ValueError('%s: select term %r: 0 <= rin < rout <= 2 (fractions of the short side)' % (who, term))
+        elif kind in WAND_CONN:
+            if len(v) not in (2, 3):
+                raise ValueError('%s: select term %r takes a seed x, y and an optional tolerance' % (who, term))
+            if not (0.0 <= v[0] <= 1.0 and 0.0 <= v[1] <= 1.0):
+                raise ValueError('%s: select term %r: the seed lies in [0, 1] (fractions of the frame): it has to be inside it' % (who, term))
+            if len(v) == 3 and not 0.0 <= v[2] <= 1.0:
+                raise ValueError('%s: select term %r: the tolerance lies in [0, 1] (a fraction of full scale)' % (who, term))
         else:
-            raise ValueError('%s: select term %r: the kind is one of lum, sat, hue, linear, radial' % (who, term))
+            raise ValueError('%s: select term %r: the kind is one of lum, sat, hue, linear, radial, wand, wand8' % (who, term))
     return terms
+
+
+WAND_CONN = {'wand': 4, 'wand8': 8}
+WAND_TOL = 0.125                                         # the byte 32
+
+
+def wand_keys(term_lists):
+    """The distinct region jobs of integer term lists (select_terms), in order of appearance: [(sx, sy, tol, conn)]."""
+    keys = []
+    for terms in term_lists:
+        for t in terms:
+            if t[0] in WAND_CONN and t[2:5] + (WAND_CONN[t[0]],) not in keys:
+                keys.append(t[2:5] + (WAND_CONN[t[0]],))
+    return keys
+
+
+def wand_resolved(terms, offset_of):
+    """Integer terms with every wand term replaced by the 'plane' term that reads its region plane: it keeps the invert
+    flag.  offset_of: {(sx, sy, tol, conn): byte offset of the plane in the tensor select_u8 takes as src}."""
+    return [('plane', t[1], offset_of[t[2:5] + (WAND_CONN[t[0]],)]) if t[0] in WAND_CONN else t for t in terms]
+
+
+def region_planes(dev_buffer, photo_offset, h, w, keys, offsets):
+    """The region planes of one photo, written into dev_buffer itself: functional.region_u8 once per 4 jobs."""
+    jobs = [(photo_offset, off, h, w) + key for key, off in zip(keys, offsets)]
+    for a in range(0, len(jobs), T.REGION_MAX_JOBS):
+        T.region_u8(dev_buffer, jobs[a:a + T.REGION_MAX_JOBS], out=dev_buffer)
+
+
+def upload_with_room(buffer, descs, room, device):
+    """functional.upload_packed with `room` more bytes behind the packed buffer ON THE DEVICE: the device buffer is
+    allocated with the room and the packed host buffer copied into its head, so that no byte is uploaded for the room."""
+    whole = torch.empty(buffer.numel() + room, dtype=torch.uint8, device=device)
+    whole[:buffer.numel()].copy_(buffer, non_blocking=True)
+    return T.upload_packed(whole, descs, device)
 
 
 def select_terms(terms, h, w, who='edit_image'):
     """A selection in user units (check_select_terms) -> the integer terms of functional.select_u8 for an (h, w) photo:
     floor(v * scale + 0.5) in double with scale 255 for lum / sat, 1536 / 360 for hue (bounds modulo 1536), w - 1 and
-    h - 1 for positions, min(h, w) for radii.  A gradient that collapses on this size is a ValueError."""
+    h - 1 for positions, min(h, w) for radii.  A gradient that collapses on this size is a ValueError.  A wand term becomes
+    ('wand' | 'wand8', invert, sx, sy, tol) with sx, sy the seed pixel and tol a byte: no term of select_u8's, but a job of
+    functional.region_u8 whose plane the caller hands to select_u8 (wand_keys, wand_resolved)."""
     if h > 65535 or w > 65535:
         raise ValueError('%s: a selection takes photos up to 65535 pixels a side, got %d x %d' % (who, w, h))
     out = []
@@ -196,6 +242,8 @@ def select_terms(terms, h, w, who='edit_image'):
             p = [_round_unit(v[0], w - 1), _round_unit(v[1], h - 1), _round_unit(v[2], w - 1), _round_unit(v[3], h - 1)]
             if p[:2] == p[2:]:
                 raise ValueError('%s: select term %r: the end points fall on one pixel of a %d x %d photo' % (who, term, w, h))
+        elif kind in WAND_CONN:
+            p = [_round_unit(v[0], w - 1), _round_unit(v[1], h - 1), _round_unit(v[2] if len(v) == 3 else WAND_TOL, 255.0)]
         else:
             p = [_round_unit(v[0], w - 1), _round_unit(v[1], h - 1), _round_unit(v[2], min(h, w)), _round_unit(v[3], min(h, w))]
             if not p[2] < p[3]:
@@ -308,6 +356,15 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, 
     the replay then read as they read the uploaded planes.  A key that also has a painted mask gets the product of the two
     (the intersection); a key with only a painted mask keeps it; feather may name either.  Nothing but the photo (and the
     painted planes) is uploaded.  Wrong specifications raise ValueError before any device use (select_plan).
+    A 'wand' / 'wand8' term is the CONNECTED region around a seed pixel -- "this sky, not the lake of the same blue": the
+    pixels joined to the seed by 4- / 8-connected steps over pixels whose three bytes each differ from the seed's by at most
+    the tolerance.  The distinct (seed, tolerance, connectivity) of the call each become one job of functional.region_u8
+    (three launches per 4 jobs, in front of the select launch; lock-free union-find in which no workgroup waits for another
+    and every loop follows strictly falling indices: include/t2onet_hip.h); their hard 0 / 255 planes are written into room
+    reserved ON THE DEVICE behind the photo and the painted planes -- no byte is uploaded for it -- and the select launch
+    reads each as a 'plane' term with the term's invert flag.  refine and feather soften them like any plane.  The order of
+    the stages is region, select, refine, feather, proxy, replay.  Without a wand term the call issues exactly the launches
+    and the one upload it issued before there was one.
     refine: None, a radius in pixels of the photo (every plane), (radius, eps), or {key of masks / select: either} -- the
     planes are snapped to the photo's own edges by functional.refine_u8's exact integer guided filter (guide = the photo's
     luminance; eps, a fraction of full scale in (0, 1], default 0.02, is how much contrast counts as an edge) IN PLACE in
@@ -331,7 +388,16 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, 
     mask_offsets = []
     if masks is not None:
         buffer, mask_offsets = _append_planes(buffer, planes)
-    dev_buffer, table_ptr, descs, _keep = T.upload_packed(buffer, descs, dev)
+    wands = wand_keys([terms for terms, _ in specs]) if plan is not None else []
+    if wands:
+        # room for the region planes behind the photo and the painted planes, on the device only: select_u8 reads plane
+        # terms from the tensor it takes as src
+        wand_offsets = [buffer.numel() + k * h * w for k in range(len(wands))]
+        dev_buffer, table_ptr, descs, _keep = upload_with_room(buffer, descs, len(wands) * h * w, dev)
+        region_planes(dev_buffer, int(descs[0]['offset']), h, w, wands, wand_offsets)
+        specs = [(wand_resolved(terms, dict(zip(wands, wand_offsets))), slot) for terms, slot in specs]
+    else:
+        dev_buffer, table_ptr, descs, _keep = T.upload_packed(buffer, descs, dev)
     mask_buffer = dev_buffer                                    # where the replay and the proxy read the planes
     if plan is not None:
         # every plane of the call in ONE launch: a rule, a rule times its painted plane, or a painted plane alone

@@ -20,7 +20,9 @@ given under; without a name every mask is feathered.  The record then also holds
 the device from the photo's own bytes (edit.edit_image's `select`).  TERM is one of lum:LO:HI[:SOFT], sat:LO:HI[:SOFT]
 (fractions in [0, 1]), hue:LO:HI[:SOFT] (degrees; the arc runs upward from LO to HI and may wrap), linear:X0,Y0:X1,Y1
 (full weight at the first point, none at the second; fractions of the frame), radial:CX,CY:RIN:ROUT (radii in fractions
-of the short side); a leading '!' inverts a term, '+' multiplies terms (at most 4).  NAME is as for --mask; a --select
+of the short side), wand:X,Y[:TOL] or wand8:X,Y[:TOL] (the magic wand: the 4- / 8-connected region around the seed at
+fractions X, Y of the frame, both in [0, 1], of the pixels whose bytes differ from the seed's by at most TOL of full
+scale, default 0.125; a hard plane that --refine and --feather soften); a leading '!' inverts a term, '+' multiplies terms (at most 4).  NAME is as for --mask; a --select
 and a --mask under the same name are intersected; --feather NAME= may name a --select as well.  The record then also
 holds 'select': {name or 'all': the terms as given}, which apply_cli replays on other photos of any size.
 
@@ -153,9 +155,13 @@ def parse_select_terms(spec):
     for text in spec.split('+'):
         fields = text.split(':')
         kind = fields[0].lstrip('!')
-        if kind not in ('lum', 'sat', 'hue', 'linear', 'radial') or len(fields[0]) - len(kind) > 1:
-            raise ValueError('--select %s: %r is not a term (lum, sat, hue, linear or radial, with ! in front to invert)' % (spec, text))
+        if kind not in ('lum', 'sat', 'hue', 'linear', 'radial', 'wand', 'wand8') or len(fields[0]) - len(kind) > 1:
+            raise ValueError('--select %s: %r is not a term (lum, sat, hue, linear, radial, wand or wand8, with ! in front to invert)' % (spec, text))
         shape = {'linear': (2, 2), 'radial': (2, 1, 1)}.get(kind)
+        if kind in ('wand', 'wand8'):
+            if len(fields) not in (2, 3):
+                raise ValueError('--select %s: %s takes X,Y[:TOL], got %r' % (spec, kind, text))
+            shape = (2, 1)[:len(fields) - 1]
         if shape is None and len(fields) not in (3, 4):
             raise ValueError('--select %s: %s takes LO:HI[:SOFT], got %r' % (spec, kind, text))
         if shape is not None and len(fields) != 1 + len(shape):
@@ -272,7 +278,9 @@ def main(argv=None):
                          'a --mask was given under, without it every mask; repeatable')
     ap.add_argument('--select', action='append', default=None, metavar='[NAME=]TERM[+TERM...]',
                     help='a local edit by a rule instead of a mask file: lum:LO:HI[:SOFT], sat:LO:HI[:SOFT], hue:LO:HI[:SOFT], '
-                         'linear:X0,Y0:X1,Y1, radial:CX,CY:RIN:ROUT, ! in front inverts, + multiplies; NAME as for --mask; repeatable')
+                         'linear:X0,Y0:X1,Y1, radial:CX,CY:RIN:ROUT, wand:X,Y[:TOL] / wand8:X,Y[:TOL] (the 4- / 8-connected region '
+                         'around the seed at fractions X, Y of the frame, tolerance TOL in [0, 1], default 0.125), ! in front '
+                         'inverts, + multiplies; NAME as for --mask; repeatable')
     ap.add_argument('--refine', action='append', default=None, metavar='[NAME=]RADIUS[:EPS]',
                     help='snap a plane to the photo\'s own edges on the device (guided filter, window RADIUS <= 64 pixels, EPS in '
                          '(0, 1], default 0.02) before it is feathered and used; NAME = a name a --mask or --select was given '

@@ -2547,3 +2547,82 @@ def refine_u8(photo_u8, buffer, jobs, out=None):
     rc = lib.t2o_refine_u8(_ptr(photo_u8), _ptr(buffer), _ptr(out), table, len(jobs), _ptr(ws), ws.numel(), _stream(buffer.device))
     replay_status(rc, 't2o_refine_u8')
     return out
+
+
+# ---- the magic wand (t2o_region.hip): the connected region around a seed pixel, union-find labelling on the device ----
+
+REGION_MAX_JOBS, REGION_LAUNCHES = 4, 3
+
+
+class RegionJob(ctypes.Structure):
+    """t2o_region_job_t of include/t2onet_hip.h (field for field)."""
+    _fields_ = [('photo_offset', ctypes.c_longlong), ('out_offset', ctypes.c_longlong), ('h', ctypes.c_int), ('w', ctypes.c_int),
+                ('seed_x', ctypes.c_int), ('seed_y', ctypes.c_int), ('tol', ctypes.c_int), ('conn', ctypes.c_int)]
+
+
+def region_jobs(jobs):
+    """jobs: a sequence of (photo_offset, out_offset, h, w, seed_x, seed_y, tol, conn) -> the ctypes array t2o_region_u8
+    takes.  Integers only; a value that does not fit its field is a ValueError."""
+    arr = (RegionJob * max(len(jobs), 1))()
+    for c, job in zip(arr, jobs):
+        if len(job) != 8:
+            raise ValueError('region_u8: a job is (photo_offset, out_offset, h, w, seed_x, seed_y, tol, conn), got %r' % (job,))
+        values = [int(v) for v in job]
+        if any(v != f for v, f in zip(values, job)):
+            raise ValueError('region_u8: job %r holds a value that is not an integer' % (job,))
+        if not all(-2 ** 63 <= v < 2 ** 63 for v in values[:2]) or not all(-2 ** 31 <= v < 2 ** 31 for v in values[2:]):
+            raise ValueError('region_u8: a value of job %r does not fit its field' % (job,))
+        c.photo_offset, c.out_offset, c.h, c.w, c.seed_x, c.seed_y, c.tol, c.conn = values
+    return arr
+
+
+_region_ws = {}
+
+
+def _region_workspace(need, device):
+    """The parent array of region_u8: cached per device and stream like _refine_workspace, a buffer of its own -- 4 bytes
+    per pixel of every job of the call."""
+    return _scratch(need, device, _region_ws, 16)
+
+
+def region_u8(photo_u8, jobs, out=None):
+    """The connected region around a seed pixel as a hard 0 / 255 plane, on the device in THREE launches whatever the number
+    of jobs and whatever the pictures hold (t2o_region_u8): job j = (photo_offset, out_offset, h, w, seed_x, seed_y, tol,
+    conn) reads the (h, w, 3) uint8 RGB photo at byte photo_offset of the 1-D uint8 GPU tensor photo_u8 (jobs may share a
+    photo) and writes 255 at byte out_offset + y w + x of `out` (allocated to fit when None) where pixel (y, x) is joined to
+    the seed by a path of pixels whose three bytes each differ from the seed's by at most tol (0..255), else 0; conn = 4
+    allows horizontal and vertical steps, 8 diagonal ones too.  The seed's bytes are read on the device.  Any byte alignment;
+    out may be photo_u8.  At most 4 jobs; a destination may overlap neither another one nor a photo of the call.  The
+    labelling is lock-free union-find in which no workgroup waits for another and every loop follows strictly falling
+    indices (include/t2onet_hip.h); the bytes are deterministic.  Every offset and size is checked here against the tensors,
+    so that a wrong argument is a ValueError and never a GPU fault.  Returns out (1-D uint8)."""
+    def ok(t):
+        return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    if not ok(photo_u8):
+        raise ValueError('region_u8: photo must be a contiguous uint8 GPU tensor')
+    jobs = [tuple(j) for j in jobs]
+    if not 1 <= len(jobs) <= REGION_MAX_JOBS:
+        raise ValueError('region_u8: 1 to 4 jobs per call, got %d' % len(jobs))
+    table = region_jobs(jobs)
+    live = [(j, c) for j, c in enumerate(table[:len(jobs)]) if c.h > 0 and c.w > 0]          # (an empty plane: the library refuses it)
+    for j, c in enumerate(table[:len(jobs)]):                                                # before `out` is allocated to fit
+        if c.out_offset < 0:
+            raise ValueError('region_u8: job %d writes before the output (out_offset %d)' % (j, c.out_offset))
+    for j, c in live:
+        if not (0 <= c.photo_offset and c.photo_offset + 3 * c.h * c.w <= photo_u8.numel()):
+            raise ValueError('region_u8: job %d reads outside the %d-byte photo buffer' % (j, photo_u8.numel()))
+        if not (0 <= c.seed_x < c.w and 0 <= c.seed_y < c.h):
+            raise ValueError('region_u8: job %d has its seed (%d, %d) outside the %d x %d frame' % (j, c.seed_x, c.seed_y, c.w, c.h))
+    need = max([c.out_offset + c.h * c.w for _, c in live] or [1])
+    if out is None:
+        out = torch.empty(need, dtype=torch.uint8, device=photo_u8.device)
+    elif not (ok(out) and out.device == photo_u8.device):
+        raise ValueError('region_u8: out must be a contiguous uint8 GPU tensor on the photo\'s device')
+    if out.numel() < need:
+        raise ValueError('region_u8: a job writes outside the %d-byte output' % out.numel())
+    lib = _lib.load()
+    need = lib.t2o_region_workspace_bytes(table, len(jobs))      # 0 for a table the library refuses: it says why below
+    ws = _region_workspace(need, photo_u8.device)
+    rc = lib.t2o_region_u8(_ptr(photo_u8), _ptr(out), table, len(jobs), _ptr(ws), ws.numel(), _stream(photo_u8.device))
+    replay_status(rc, 't2o_region_u8')
+    return out
