@@ -1025,6 +1025,58 @@ size_t t2o_region_workspace_bytes(const t2o_region_job_t* jobs, int J);
 int t2o_region_u8(const unsigned char* photo, unsigned char* out, const t2o_region_job_t* jobs, int J,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- removing a region of a photo on the device (t2o_fill.hip): the pixels under a plane replaced by a PUSH-PULL FILL
+ * from the pixels around them.  A classical, exact, deterministic smooth fill: it suits sky, walls and blurred
+ * backgrounds, synthesises no texture, and is NOT the reference's inpaint_obj operator (a network).  Job j reads the
+ * (h,w,3) uint8 RGB photo P at photo + photo_offset and the (h,w) uint8 plane M at plane + plane_offset and writes (h,w,3)
+ * uint8 at out + out_offset (all three at any byte alignment; no byte outside the destination is written).  Integers
+ * only; // is FLOOR division:
+ *   known(y, x) <=> M = 0                                  only fully kept pixels are sources
+ *   levels      level 0 is the picture; level k+1 has size (ceil(h_k / 2), ceil(w_k / 2)), down to 1 x 1 = level K;
+ *               colours are carried in sixteenths: 0..4080, uint16
+ *   pull        C_0 = 16 P where known.  A cell of level k+1 has the children (2y+a, 2x+b), a, b in {0, 1}, that lie inside
+ *               level k; n = the number of known ones; the cell is known <=> n > 0;
+ *               C_{k+1} = (sum of C_k over the known children + n // 2) // n, per channel
+ *   push        F_K = C_K; for k = K-1 .. 0: F_k = C_k where the cell is known, otherwise U_k, the 9/3/3/1 tent over F_{k+1}:
+ *               Y = y >> 1, X = x >> 1, Yn = clamp(Y + (y odd ? 1 : -1), 0, h_{k+1} - 1), Xn likewise,
+ *               U = (9 F[Y,X] + 3 F[Y,Xn] + 3 F[Yn,X] + F[Yn,Xn] + 8) >> 4
+ *   result      fill = (F_0 + 8) >> 4;  out = P where M = 0, otherwise out = (P (255 - M) + fill M + 127) // 255.
+ *               If the top cell is unknown (no pixel has M = 0) then out = P everywhere: decided on the device, no host read.
+ * Exact consequences: kept pixels come out byte for byte; M == 0 everywhere is a copy; every filled channel lies within
+ * [min, max] of that channel over the known pixels (rounding half up cannot leave the range); a surround of one colour
+ * fills the hole with exactly that colour, whatever lies under the hole; transposing photo and plane transposes the output;
+ * a picture with one known pixel is filled with that pixel's colour.  (Flips are NO symmetry: the pyramid is anchored at the
+ * top-left.)  A feathered or refined plane has M > 0 in its soft band, so softening a selection also keeps the object's
+ * anti-aliased rim out of the sources.
+ * T2O_FILL_LAUNCHES = THREE launches cover all jobs, whatever the pictures hold.  (1) pull: a workgroup per 64 x 64 tile
+ * (tiles start at multiples of 64, so child pairs stay inside a tile up to level 6) reads photo and plane once, builds levels
+ * 1..6 in LDS and stores them in the workspace, 8 bytes per cell (3 x uint16 + known): about 8/3 bytes per pixel.  (2) top: ONE
+ * workgroup per job pulls levels 7..K and pushes K..6 through the workspace, __threadfence() + __syncthreads() between two
+ * levels, F in arrays of its own, every array on a 128-byte line of its own; the known field of C_K's cell is the "empty" flag.
+ * (3) push + blend: a workgroup per tile; a tile without a byte M > 0, or any tile of an empty job, copies its bytes -- or
+ * returns at once when the job is in place; another reads the 3 x 3 neighbourhood of F_6 and a one-cell halo of levels 5..1
+ * (enough: a halo cell's tent always leans towards the tile), pushes down in LDS and stores aligned dwords, single bytes at the
+ * two ends of a misaligned row range.  Pass (3) reads level-0 bytes of its own tile only, so a job may run IN PLACE:
+ * out + out_offset == photo + photo_offset.
+ * No workgroup waits for another (no flag, no spin, no grid barrier); every loop bound is fixed by the sizes alone; no
+ * atomics, no float, no scratch, no inline assembly; no allocation, no host synchronisation; capturable, deterministic.
+ * jobs: HOST array of 1 <= J <= 4, copied into the kernel arguments; jobs may share a photo or a plane.  workspace: DEVICE,
+ * 16-byte aligned, t2o_fill_workspace_bytes (the arrays above, each rounded up to 128 bytes, plus 112 to round the base up;
+ * 0 for a job table that t2o_fill_u8 would refuse).  The caller guarantees that offsets and sizes lie inside photo / plane / out.
+ * T2O_EINVAL, before any launch: null pointers, J outside 1..4, non-positive sizes, 3 h w >= 2^31, a side above 4194240
+ * (65535 tiles), negative offsets, a destination that overlaps (by address) another destination, a plane of the call, or a photo of the call -- except the
+ * job's OWN photo at exactly its own address, the in-place case (a photo that another job of the call also reads is that
+ * job's photo too: it cannot be a destination).  T2O_EWORKSPACE: workspace null, too small or not 16-byte aligned. */
+#define T2O_FILL_MAX_JOBS 4
+#define T2O_FILL_LAUNCHES 3
+typedef struct {
+  long long photo_offset, plane_offset, out_offset;   /* first byte of the photo / the plane / the destination, counted from photo / plane / out */
+  int h, w;
+} t2o_fill_job_t;
+size_t t2o_fill_workspace_bytes(const t2o_fill_job_t* jobs, int J);
+int t2o_fill_u8(const unsigned char* photo, const unsigned char* plane, unsigned char* out, const t2o_fill_job_t* jobs, int J,
+                void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the metrics of the test loop in one call: utils/eval.py:50-60 (ImageEvaluator.update: input / output L1 and SSIM),
  * utils/ssim/__init__.py:20-40 (the SSIM itself) and test_seq2seqL1.py:60-74 (the END-image select and the two L1
  * distances the loop averages).  imgs: HOST array of 1 <= T <= 8 device pointers to (B,C,H,W) step images, first: device

@@ -172,6 +172,8 @@ SIGNATURES = {
     't2o_refine_u8': (_I, [_P, _P, _P, _P, _I, _P, _Z, _P]),
     't2o_region_workspace_bytes': (_Z, [_P, _I]),
     't2o_region_u8': (_I, [_P, _P, _P, _I, _P, _Z, _P]),
+    't2o_fill_workspace_bytes': (_Z, [_P, _I]),
+    't2o_fill_u8': (_I, [_P, _P, _P, _P, _I, _P, _Z, _P]),
     't2o_eval_metrics_workspace_bytes': (_Z, [_I, _I, _I, _I]),
     't2o_eval_metrics': (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _Z, _I, _I, _I, _I, _P]),
     't2o_end_select_var_mean_workspace_bytes': (_Z, [_Z]),

@@ -23,8 +23,12 @@ functional.select_u8 launch writes the planes, functional.feather_u8's two launc
 ONE functional.replay_u8_any launch replays the list under them.  The new records carry 'select' and 'feather' along.
 A record that also has 'refine' (edit_cli --refine: {one of those names or 'all': [radius, eps]}) snaps each photo's planes
 to that photo's OWN luminance: functional.refine_u8's four launches run between the select launch and feather's two.
+A record that has 'fill' (edit_cli --fill: the name of a plane) and 'select' under that name REMOVES what lies under that
+plane from every photo first: the plane is made per photo like the others (its own seed pixel, its own luminance, its own
+size), functional.fill_u8 fills the photos of a group in place in ONE call of three launches, and the list is then
+replayed on the filled photos.  A smooth fill, not the reference's inpaint network: an 'inpaint' OPERATION stays refused.
 Painted masks do not carry from photo to photo: a record with 'masks' and no 'select' is replayed globally, as before,
-and a record that has both is refused.
+and a record that has both is refused -- and so is a record whose 'fill' names a painted mask, or nothing.
 """
 import argparse
 import json
@@ -104,42 +108,67 @@ def parse_refine(record):
                              info['select'])
 
 
-def local_planes(ops, select, feather, refine=None):
+def parse_fill(record):
+    """The 'fill' of a record -> None, or the name of the selection whose content is removed from every photo.  Raises
+    ValueError naming the entry: a name whose plane is a painted mask (it stays with its photo), a name without a plane."""
+    info = record[0] if isinstance(record, list) and record else record
+    fill = info.get('fill') if isinstance(info, dict) else None
+    if fill is None:
+        return None
+    if not isinstance(fill, str):
+        raise ValueError('record: \'fill\' is the name a selection goes by, got %r' % (fill,))
+    select, masks = info.get('select'), info.get('masks')
+    if isinstance(select, dict) and fill in select:
+        return fill
+    if isinstance(masks, dict) and fill in masks:
+        raise ValueError('record: \'fill\': %r names the painted mask %r, which belongs to one photo and is not carried to others '
+                         '(edit_cli --mask stays with its photo); only a \'select\' entry can be filled on other photos' % (fill, masks[fill]))
+    raise ValueError('record: \'fill\': %r names no entry of \'select\' (given: %s)'
+                     % (fill, ', '.join(sorted(select)) if isinstance(select, dict) and select else 'none'))
+
+
+def local_planes(ops, select, feather, refine=None, fill=None):
     """Which planes a photo needs for `ops` under parse_local's (select, feather) -> ([(terms in user units, sigma)],
     mask_of): the distinct planes, and per step the plane's number or -1.  A named entry wins over 'all', in select and in
     feather alike: an 'all' sigma stands for every plane that has none of its own (edit_cli.feather_argument).  With
-    parse_refine's `refine` a plane is (terms, sigma, (radius, eps) or None), named entries winning in the same way."""
+    parse_refine's `refine` a plane is (terms, sigma, (radius, eps) or None), named entries winning in the same way.  With
+    parse_fill's `fill` a third value follows: the number of that name's plane, which is made whether an operation uses it
+    or not and counts towards the 4."""
     from .edit_cli import parse_select_terms
     planes, mask_of = [], []
-    for op in ops:
-        name = ACTIONS[op] if ACTIONS[op] in select else 'all'
-        if name not in select:
-            mask_of.append(-1)
-            continue
+
+    def plane_of(name):
         plane = (tuple(parse_select_terms(select[name])), float(feather.get(name, feather.get('all', 0.0))))
         if refine is not None:
             pair = refine.get(name, refine.get('all'))
             plane += (tuple(pair) if pair is not None and pair[0] > 0 else None,)
         if plane not in planes:
             planes.append(plane)
-        mask_of.append(planes.index(plane))
+        return planes.index(plane)
+    for op in ops:
+        name = ACTIONS[op] if ACTIONS[op] in select else 'all'
+        mask_of.append(plane_of(name) if name in select else -1)
+    if fill is not None:
+        fill_no = plane_of(fill)
     if len(planes) > MAX_PLANES:
-        raise ValueError('record: the operations name %d distinct selections, the replay takes %d' % (len(planes), MAX_PLANES))
-    return planes, mask_of
+        raise ValueError('record: the operations%s name %d distinct selections, the replay takes %d'
+                         % (' and \'fill\'' if fill is not None else '', len(planes), MAX_PLANES))
+    return (planes, mask_of) if fill is None else (planes, mask_of, fill_no)
 
 
-def apply_record_local(images, ops, params, select, feather, multi_img=False, device=None, refine=None):
+def apply_record_local(images, ops, params, select, feather, multi_img=False, device=None, refine=None, fill=None):
     """apply_record under the selections of parse_local: the same result layout.  One upload; per group of photos that
     together name at most 4 planes: one select_u8 launch, refine_u8's four where parse_refine's `refine` gives a radius,
     feather_u8 where a sigma is given, one replay launch.  A 'wand' / 'wand8' term is resolved per photo at that photo's
     size: its seed pixel from the fractions of the rule, one functional.region_u8 job per distinct (seed, tolerance,
     connectivity) of the photo, in calls of at most 4 in front of the group's select launch; the region planes lie in room
     reserved on the device behind the uploaded buffer (no byte is uploaded for it), where the select launch reads them as
-    'plane' terms."""
+    'plane' terms.  With parse_fill's `fill` the photos of a group are filled in place under their own plane of that name by
+    one functional.fill_u8 call, behind feather and in front of the replay."""
     from . import functional as T
     from .edit import refine_eps2, select_terms, upload_with_room, wand_keys, wand_resolved
     assert (MAX_STEPS, MAX_JOBS, PARAM_PAD, MAX_PLANES) == (T.REPLAY_MAX_STEPS, T.REPLAY_MAX_JOBS, T.PARAM_PAD, T.REPLAY_MAX_MASKS)
-    planes, mask_of = local_planes(ops, select, feather, refine or None)
+    planes, mask_of, *fill_no = local_planes(ops, select, feather, refine or None, fill)
     snaps = [(p[2][0], refine_eps2(p[2][1])) if len(p) == 3 and p[2] else None for p in planes]      # before any device use
     planes = [p[:2] for p in planes]
     if not planes:                                                    # no operation of the list is selected for
@@ -190,6 +219,8 @@ def apply_record_local(images, ops, params, select, feather, multi_img=False, de
             T.refine_u8(dev_buffer, plane_buffer, snap_jobs)
         if soft_jobs:
             T.feather_u8(plane_buffer, soft_jobs)
+        if fill_no:                                                   # at most 4 photos to a group: one call
+            T.fill_u8(dev_buffer, plane_buffer, [(offsets[i], sel_jobs[where[i, fill_no[0]]][1], offsets[i]) + shapes[i] for i in group], out=dev_buffer)
         out = T.replay_u8_any(dev_buffer, jobs, row.unsqueeze(0).expand(len(jobs), -1, -1).contiguous(), plane_buffer,
                               [job[1] for job in sel_jobs]).cpu().numpy()
         for i in group:
@@ -258,14 +289,15 @@ def main(argv=None):
     request, ops, params = parse_record(record)                       # before any decode or device use
     local = parse_local(record)
     refine = parse_refine(record)
+    fill = parse_fill(record)
     images = [decode_image(p) for p in args.img]
     from .edit_cli import write_outputs
     infos = []
     if local is None:
         results, carried = apply_record(images, ops, params, args.multi_img), {}
     else:
-        results = apply_record_local(images, ops, params, local[0], local[1], args.multi_img, refine=refine)
-        carried = {'select': local[0], 'feather': local[1] or None}
+        results = apply_record_local(images, ops, params, local[0], local[1], args.multi_img, refine=refine, fill=fill)
+        carried = {'select': local[0], 'feather': local[1] or None, 'fill': fill}
         if refine:
             carried['refine'] = refine
     for path, img, steps in zip(args.img, images, results):

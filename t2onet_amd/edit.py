@@ -260,14 +260,15 @@ def _key_targets(key, what):
     raise ValueError('edit_image: %s key %r is neither \'all\' nor an executor operator index 0..7' % (what, key))
 
 
-def select_plan(select, masks, feather, h, w, refine=None):
+def select_plan(select, masks, feather, h, w, refine=None, keys=None):
     """The planes of an edit_image call that gives `select` -- checked without any device use.  select: {executor operator
     index or 'all': selection in user units}, keyed like masks.  Every key of select or masks gets a plane: its selection,
     multiplied by its painted mask when the SAME key has one (a 'plane' term: the intersection); a key with only a painted
     mask is a one-term 'plane' job.  Keys whose rule and painted plane agree share a plane.  Returns (painted, specs, by_op,
     sigma_of): the distinct painted planes to upload, per plane (integer terms, number of its painted plane or None),
     {operator index: plane number} ('all' first, an entry for one operator wins), {plane number: sigma > 0}.  With `refine`
-    (keyed like feather; checked_refine) a fifth value follows: {plane number: (radius > 0, E)}."""
+    (keyed like feather; checked_refine) a fifth value follows: {plane number: (radius > 0, E)}.  keys: a dict that receives
+    {key of select or masks: plane number}."""
     if not isinstance(select, dict) or not select:
         raise ValueError('edit_image: select is {executor operator index or \'all\': [terms]}')
     masks = masks or {}
@@ -295,6 +296,8 @@ def select_plan(select, masks, feather, h, w, refine=None):
         tokens[key] = specs.index((terms, slot))
     if len(specs) > T.REPLAY_MAX_MASKS:
         raise ValueError('edit_image: %d distinct planes, the replay takes %d' % (len(specs), T.REPLAY_MAX_MASKS))
+    if keys is not None:
+        keys.update(tokens)
     handles = [object() for _ in specs]                               # checked_feather tells planes apart by identity
     by_handle = checked_feather(feather, {key: handles[no] for key, no in tokens.items()})
     sigma_of = {no: by_handle[id(hd)] for no, hd in enumerate(handles) if id(hd) in by_handle}
@@ -327,7 +330,18 @@ def _proxy_mask_dict(dev_buffer, mask_offsets, by_op, size, proxy_size):
     return [{str(op + 3): [proxies[slot]] for op, slot in by_op.items()}]
 
 
-def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, select=None, refine=None):
+def checked_fill(fill, masks, select):
+    """fill (None, or a key that masks or select also carries) -> the key; anything else is a ValueError."""
+    if fill is None:
+        return None
+    _key_targets(fill, 'fill')
+    if fill not in (masks or {}) and fill not in (select or {}):
+        raise ValueError('edit_image: fill key %r names no plane (masks: %s; select: %s)'
+                         % (fill, ', '.join(repr(k) for k in masks or {}) or 'none', ', '.join(repr(k) for k in select or {}) or 'none'))
+    return fill
+
+
+def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, select=None, refine=None, fill=None):
     """img_u8_hwc: the decoded photo, uint8 (h,w,3) RGB (array or CPU tensor); x: (1, L) request token ids.
     Returns (steps_u8, ops, params):
       steps_u8  (max(n,1), h, w, 3) uint8 GPU tensor: picture k is the photo after the first k+1 of the n chosen operators,
@@ -370,12 +384,26 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, 
     luminance; eps, a fraction of full scale in (0, 1], default 0.02, is how much contrast counts as an edge) IN PLACE in
     the buffer the later stages read: after select, before feather, the proxy's mask_dict and the replay, so that the
     proxy's decision and the native replay see the same plane.  Four launches, whatever the number of planes.  Keys that
-    share one plane must agree; refine without masks or select is an error; None is the path without it, launch for launch."""
+    share one plane must agree; refine without masks or select is an error; None is the path without it, launch for launch.
+    fill: None, or a key that masks or select also carries -- the natural one is 4, the inpaint slot; any operator index or
+    'all' is allowed, and the plane then also localises those operators as it does without fill.  What lies under that
+    plane is REMOVED from the photo: the plane is made exactly as above (region, select, refine, feather), then
+    functional.fill_u8 (three launches) replaces every pixel whose plane byte M is > 0, blended by M / 255, with the exact
+    integer push-pull fill of include/t2onet_hip.h from the pixels with M = 0 -- IN PLACE in the device buffer, before the proxy
+    is made.  The actor therefore decides on the filled picture, the replay edits the filled picture, and every picture of
+    steps_u8 carries the fill.  The order of the stages is region, select, refine, feather, fill, proxy, replay: wand seeds
+    and select rules read the ORIGINAL bytes.  A soft plane has M > 0 in its soft band, so refine and feather also keep the
+    object's anti-aliased rim out of the fill's sources.  The fill plane counts towards the four planes of a call.  It is a
+    SMOOTH fill -- sky, walls, blurred backgrounds; it synthesises no texture and is not the reference's inpaint_obj network,
+    which stays unexecutable here (operators.InpaintOperator).  A fill key without a plane is a ValueError before any device
+    use; None is the path without it, launch for launch and upload for upload."""
     img = T._u8_hwc(img_u8_hwc)
     h, w = img.shape[:2]
-    plan = select_plan(select, masks, feather, h, w, refine if refine is not None else {}) if select is not None else None    # before any device use
+    plane_of = {}
+    plan = select_plan(select, masks, feather, h, w, refine if refine is not None else {}, plane_of) if select is not None else None    # before any device use
     sigma_of = checked_feather(feather, masks) if plan is None else {}                       # before any device use
     refine_of = checked_refine(refine, masks) if plan is None else {}                        # before any device use
+    fill = checked_fill(fill, masks, select)                                                 # before any device use
     dev = next(model.parameters()).device
     opt = model.opt
     slot_of = {}
@@ -414,6 +442,10 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, 
             T.refine_u8(dev_buffer, dev_buffer, [(int(descs[0]['offset']),) + (mask_offsets[slot_of[p]],) * 2 + (h, w, r, E) for p, (r, E) in refine_of.items()])
         if sigma_of:
             T.feather_u8(dev_buffer, [(mask_offsets[slot_of[p]],) * 2 + (h, w, sigma) for p, sigma in sigma_of.items()])
+    if fill is not None:
+        # the photo filled in place under its finished plane: the proxy and the replay below read the filled bytes
+        at = mask_offsets[plane_of[fill] if plan is not None else slot_of[id(masks[fill])]]
+        T.fill_u8(dev_buffer, mask_buffer, [(int(descs[0]['offset']), at, int(descs[0]['offset']), h, w)], out=dev_buffer)
     ph, pw = short_side_size(h, w, proxy_short) if min(h, w) > proxy_short else (h, w)
     proxy = T._resize_launch(dev_buffer, table_ptr, 1, ph, pw)
     mask_dict = _proxy_mask_dict(mask_buffer, mask_offsets, by_op, (h, w), (ph, pw)) if local else None

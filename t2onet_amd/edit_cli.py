@@ -32,6 +32,15 @@ RADIUS pixels (a whole number, at most 64); EPS, a fraction of full scale in (0,
 counts as an edge.  NAME is a name a --mask or --select was given under; without a name every plane is refined.  The
 record then also holds 'refine': {name or 'all': [radius, eps]}, which apply_cli replays under each photo's own luminance.
 
+--fill [NAME] REMOVES what lies under a plane before anything else is decided: NAME is an operator name a --mask or
+--select was given under (default: inpaint, the slot of the operator this project cannot execute).  The plane is made as
+above (wand, rule, painted mask, --refine, --feather); then the pixels under it are replaced on the device, blended by the
+plane's byte, with an exact integer push-pull fill from the pixels the plane leaves at 0 (edit.edit_image's `fill`,
+functional.fill_u8).  The actor decides on the filled photo and every written picture carries the fill.  It is a SMOOTH
+fill: it suits sky, walls and blurred backgrounds, synthesises no texture and is not the reference's inpaint network.  The
+record then also holds 'fill': NAME, which apply_cli carries to other photos when the plane is a --select.  For example
+    --select 'inpaint=wand:0.5,0.4:0.1' --refine inpaint=6 --feather inpaint=2 --fill
+
 The actor decides on a proxy of the photo (short side --proxy_short, the test loader's 600; a smaller photo is its own
 proxy) and the decision is applied to the photo at its native size by the fused 8-bit replay kernel (edit.edit_image).
 
@@ -136,6 +145,16 @@ def parse_refine_args(specs, named):
     return refines
 
 
+def parse_fill_arg(name, named):
+    """--fill's value (None when the flag is absent) -> None or the name; named: every name a plane goes by.  Raises
+    ValueError when no --mask or --select was given under it."""
+    if name is None:
+        return None
+    if name not in named:
+        raise ValueError('--fill %s: no --mask or --select was given under %r (given: %s)' % (name, name, ', '.join(sorted(named)) or 'none'))
+    return name
+
+
 def refine_argument(refines, named):
     """{name or 'all': (radius, eps)} of parse_refine_args -> the `refine` argument of edit.edit_image, keyed like the planes
     of `named`.  An unnamed value stands for every plane; a named one wins over it (as feather_argument)."""
@@ -232,10 +251,10 @@ def load_masks(named, h, w):
 
 
 def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, multi_img=False, masks=None, feather=None, select=None,
-                  refine=None):
+                  refine=None, fill=None):
     """The files of one edit (see the module docstring); steps_u8: (max(n,1), h, w, 3) uint8 array; masks: {name: file}
-    of a local edit, feather: {name: sigma}, select: {name: terms as given} and refine: {name: (radius, eps)}, each recorded
-    when given.  Returns the record."""
+    of a local edit, feather: {name: sigma}, select: {name: terms as given}, refine: {name: (radius, eps)} and fill: the
+    name of the plane whose content was removed, each recorded when given.  Returns the record."""
     from PIL import Image
     name, ext = os.path.splitext(os.path.basename(img_path))
     out_dir = os.path.join(save_dir, name)
@@ -255,6 +274,8 @@ def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, mu
         info['select'] = dict(select)
     if refine:
         info['refine'] = {name: [int(v[0]), float(v[1])] for name, v in refine.items()}
+    if fill:
+        info['fill'] = str(fill)
     with open(os.path.join(out_dir, name + '.json'), 'w') as f:
         json.dump([info], f)
     return info
@@ -285,17 +306,23 @@ def main(argv=None):
                     help='snap a plane to the photo\'s own edges on the device (guided filter, window RADIUS <= 64 pixels, EPS in '
                          '(0, 1], default 0.02) before it is feathered and used; NAME = a name a --mask or --select was given '
                          'under, without it every plane; repeatable')
+    ap.add_argument('--fill', nargs='?', const='inpaint', default=None, metavar='NAME',
+                    help='remove what lies under a plane before the edit: the pixels under the plane a --mask or --select was given '
+                         'under NAME (default inpaint) are replaced on the device by a smooth push-pull fill from the pixels around '
+                         'them (sky, walls, blurred backgrounds; no texture is synthesised; not the reference\'s inpaint network)')
     args = ap.parse_args(argv)
     named = parse_mask_args(args.mask)
     rules = parse_select_args(args.select)
     planes = dict(named, **rules)                                                  # every name a plane goes by
     sigmas = parse_feather_args(args.feather, planes)                              # before the model: a wrong value fails early
     refines = parse_refine_args(args.refine, planes)
+    fill_name = parse_fill_arg(args.fill, planes)
     img = decode_image(args.img)
     masks = load_masks(named, img.shape[0], img.shape[1]) if named else None       # before the model: a wrong mask fails early
     feather = feather_argument(sigmas, planes)
     select = select_argument(rules)
     refine = refine_argument(refines, planes)
+    fill = None if fill_name is None else 'all' if fill_name == 'all' else ACTIONS.index(fill_name)
     if select:
         from .edit import select_plan
         select_plan(select, masks, feather, img.shape[0], img.shape[1], refine)    # a gradient that collapses on this photo, too many planes
@@ -314,9 +341,9 @@ def main(argv=None):
     model.load_state_dict(torch.load(args.checkpoint, map_location='cpu'), strict=False)      # as the demo (:129)
     model.to(device)
     steps_u8, ops, params = edit_image(model, img, request_to_idx(args.request, vocab2id, opt), args.proxy_short, masks=masks,
-                                      feather=feather, select=select, **({'refine': refine} if refine else {}))
+                                      feather=feather, select=select, **dict({'refine': refine} if refine else {}, **({'fill': fill} if fill is not None else {})))
     info = write_outputs(args.save_dir, args.img, args.request, img, steps_u8.cpu().numpy(), ops, params.cpu(), args.multi_img,
-                         masks=named or None, feather=sigmas or None, select=rules or None, refine=refines or None)
+                         masks=named or None, feather=sigmas or None, select=rules or None, refine=refines or None, fill=fill_name)
     print('%s: %s -> %s' % (args.request, ', '.join(n for n, _ in info['operations']) or '(no operator)',
                             os.path.join(args.save_dir, os.path.splitext(os.path.basename(args.img))[0], info['output'])))
     return info

@@ -2626,3 +2626,84 @@ def region_u8(photo_u8, jobs, out=None):
     rc = lib.t2o_region_u8(_ptr(photo_u8), _ptr(out), table, len(jobs), _ptr(ws), ws.numel(), _stream(photo_u8.device))
     replay_status(rc, 't2o_region_u8')
     return out
+
+
+# ---- removing a region (t2o_fill.hip): the pixels under a plane replaced by an exact integer push-pull fill ----
+
+FILL_MAX_JOBS, FILL_LAUNCHES = 4, 3
+
+
+class FillJob(ctypes.Structure):
+    """t2o_fill_job_t of include/t2onet_hip.h (field for field)."""
+    _fields_ = [('photo_offset', ctypes.c_longlong), ('plane_offset', ctypes.c_longlong), ('out_offset', ctypes.c_longlong),
+                ('h', ctypes.c_int), ('w', ctypes.c_int)]
+
+
+def fill_jobs(jobs):
+    """jobs: a sequence of (photo_offset, plane_offset, out_offset, h, w) -> the ctypes array t2o_fill_u8 takes.  Integers
+    only; a value that does not fit its field is a ValueError."""
+    arr = (FillJob * max(len(jobs), 1))()
+    for c, job in zip(arr, jobs):
+        if len(job) != 5:
+            raise ValueError('fill_u8: a job is (photo_offset, plane_offset, out_offset, h, w), got %r' % (job,))
+        values = [int(v) for v in job]
+        if any(v != f for v, f in zip(values, job)):
+            raise ValueError('fill_u8: job %r holds a value that is not an integer' % (job,))
+        if not all(-2 ** 63 <= v < 2 ** 63 for v in values[:3]) or not all(-2 ** 31 <= v < 2 ** 31 for v in values[3:]):
+            raise ValueError('fill_u8: a value of job %r does not fit its field' % (job,))
+        c.photo_offset, c.plane_offset, c.out_offset, c.h, c.w = values
+    return arr
+
+
+_fill_ws = {}
+
+
+def _fill_workspace(need, device):
+    """The pyramid of fill_u8: cached per device and stream like _region_workspace, a buffer of its own -- about 8/3 bytes
+    per pixel of every job of the call."""
+    return _scratch(need, device, _fill_ws, 16)
+
+
+def fill_u8(photo_u8, planes_u8, jobs, out=None):
+    """Remove what lies under a plane, on the device in THREE launches whatever the number of jobs and whatever the pictures
+    hold (t2o_fill_u8): job j = (photo_offset, plane_offset, out_offset, h, w) reads the (h, w, 3) uint8 RGB photo at byte
+    photo_offset of the 1-D uint8 GPU tensor photo_u8 and the (h, w) uint8 plane at byte plane_offset of the 1-D uint8 GPU
+    tensor planes_u8 (jobs may share either) and writes the photo with every pixel whose plane byte M is > 0 blended, by
+    M / 255, with the exact integer push-pull fill of include/t2onet_hip.h from the pixels with M = 0, at byte out_offset of
+    `out` (allocated to fit when None); pixels with M = 0 come out byte for byte, and a plane without a 0 leaves the photo as
+    it is.  A SMOOTH fill -- sky, walls, blurred backgrounds; it synthesises no texture and is not the reference's inpaint
+    network.  Any byte alignment; planes_u8 and out may be photo_u8.  At most 4 jobs; a destination may overlap neither
+    another one nor a plane nor a photo of the call, except its own photo at exactly its own address: a job in place.  No
+    workgroup waits for another and every loop bound follows from the sizes; the bytes are deterministic.  Every offset and
+    size is checked here against the tensors, so that a wrong argument is a ValueError and never a GPU fault.  Returns out
+    (1-D uint8)."""
+    def ok(t):
+        return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    if not (ok(photo_u8) and ok(planes_u8)) or photo_u8.device != planes_u8.device:
+        raise ValueError('fill_u8: photo and planes must be contiguous uint8 GPU tensors on one device')
+    jobs = [tuple(j) for j in jobs]
+    if not 1 <= len(jobs) <= FILL_MAX_JOBS:
+        raise ValueError('fill_u8: 1 to 4 jobs per call, got %d' % len(jobs))
+    table = fill_jobs(jobs)
+    live = [(j, c) for j, c in enumerate(table[:len(jobs)]) if c.h > 0 and c.w > 0]          # (an empty picture: the library refuses it)
+    for j, c in enumerate(table[:len(jobs)]):                                                # before `out` is allocated to fit
+        if c.out_offset < 0:
+            raise ValueError('fill_u8: job %d writes before the output (out_offset %d)' % (j, c.out_offset))
+    for j, c in live:
+        if not (0 <= c.photo_offset and c.photo_offset + 3 * c.h * c.w <= photo_u8.numel()):
+            raise ValueError('fill_u8: job %d reads outside the %d-byte photo buffer' % (j, photo_u8.numel()))
+        if not (0 <= c.plane_offset and c.plane_offset + c.h * c.w <= planes_u8.numel()):
+            raise ValueError('fill_u8: job %d reads outside the %d-byte plane buffer' % (j, planes_u8.numel()))
+    need = max([c.out_offset + 3 * c.h * c.w for _, c in live] or [1])
+    if out is None:
+        out = torch.empty(need, dtype=torch.uint8, device=photo_u8.device)
+    elif not (ok(out) and out.device == photo_u8.device):
+        raise ValueError('fill_u8: out must be a contiguous uint8 GPU tensor on the photo\'s device')
+    if out.numel() < need:
+        raise ValueError('fill_u8: a job writes outside the %d-byte output' % out.numel())
+    lib = _lib.load()
+    need = lib.t2o_fill_workspace_bytes(table, len(jobs))        # 0 for a table the library refuses: it says why below
+    ws = _fill_workspace(need, photo_u8.device)
+    rc = lib.t2o_fill_u8(_ptr(photo_u8), _ptr(planes_u8), _ptr(out), table, len(jobs), _ptr(ws), ws.numel(), _stream(photo_u8.device))
+    replay_status(rc, 't2o_fill_u8')
+    return out
