@@ -892,6 +892,45 @@ size_t t2o_feather_workspace_bytes(const t2o_feather_job_t* jobs, int J);
 int t2o_feather_u8(const unsigned char* src, unsigned char* out, const t2o_feather_job_t* jobs, int J, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* ---- growing, shrinking and bordering the mask planes of a local edit on the device (t2o_morph.hip): the plane's boundary
+ * moved by R pixels of EXACT Euclidean distance -- "expand the selection by 4 px, then remove".  Job j reads the (h,w)
+ * uint8 plane P at src + src_offset (any byte alignment) and writes a hard 0 / 255 (h,w) plane at out + out_offset (any byte
+ * alignment; no byte outside the plane is written).  S = {p : P[p] >= 128}; over pixels INSIDE THE FRAME ONLY
+ *   Dout(p) = min over q in S of |p - q|^2,   Din(p) = min over q not in S of |p - q|^2,   +infinity where there is no such q;
+ * the frame edge is not an edge of the selection: a sky that touches the top of the photo still touches it after a shrink.
+ * For the integer radius 0 <= R <= 64:
+ *   T2O_MORPH_GROW    255 where Dout(p) <= R^2, else 0
+ *   T2O_MORPH_SHRINK  255 where p is in S and Din(p) > R^2, else 0
+ *   T2O_MORPH_BORDER  255 where GROW is 255 and SHRINK is 0, else 0
+ * So SHRINK(P) = 255 - GROW(255 - P); GROW at R = 0 is the binarised plane and BORDER at R = 0 is all 0; an empty S gives
+ * all 0 in every mode, a full S all 255 for GROW and SHRINK and all 0 for BORDER; one set pixel grown by R = 25 is the 1961
+ * lattice points of the disc.  No approximation (no chamfer, no iterated 3 x 3 steps): integers, two passes.  The column
+ * pass writes g(y,x) = min(|dy| : |dy| <= R, (y+dy,x) in the set), or R + 1, as bytes to the workspace (the set is S for
+ * GROW, the frame outside S for SHRINK, one field of each for BORDER); the row pass uses Dout(y,x) <= R^2 <=> some |dx| <= R
+ * with x + dx in the frame has g(y,x+dx) <= c[|dx|], c[k] = floor(sqrt(R^2 - k^2)) built on the host in integer arithmetic
+ * (c^2 + k^2 <= R^2 < (c+1)^2 + k^2 is checked for each entry).
+ * Two launches cover all jobs; every source byte is read by the first before the second writes any destination byte, so
+ * a job may run in place (out + out_offset == src + src_offset) and a source may overlap any destination; the
+ * destinations of different jobs may not overlap each other.  jobs: HOST array of 1 <= J <= 4, copied with the threshold
+ * tables into the kernel arguments.  workspace: DEVICE, 8-byte aligned, t2o_morph_workspace_bytes (1 byte per pixel, 2 for
+ * BORDER, rows padded to 4 pixels; 0 for a job table that t2o_morph_u8 would refuse).  No allocation, no host
+ * synchronisation, no float, no atomics; deterministic, capturable.  The caller guarantees that offsets and sizes lie
+ * inside src / out.
+ * T2O_EINVAL, before any launch: null pointers, J outside 1..4, non-positive sizes, h * w >= 2^31, negative offsets, a radius
+ * outside 0..64, an unknown mode, overlapping destinations, a misaligned workspace.  T2O_EWORKSPACE: workspace null or too
+ * small. */
+#define T2O_MORPH_MAX_JOBS 4
+#define T2O_MORPH_MAX_RADIUS 64
+enum { T2O_MORPH_GROW = 0, T2O_MORPH_SHRINK = 1, T2O_MORPH_BORDER = 2 };
+typedef struct {
+  long long src_offset, out_offset;   /* first byte of the source / destination plane, counted from src / out */
+  int h, w;
+  int radius, mode;
+} t2o_morph_job_t;
+size_t t2o_morph_workspace_bytes(const t2o_morph_job_t* jobs, int J);
+int t2o_morph_u8(const unsigned char* src, unsigned char* out, const t2o_morph_job_t* jobs, int J, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
 /* ---- the mask planes of a local edit made from a RULE on the device (t2o_select.hip): no painted file, no host-built
  * plane, no upload of h * w bytes per plane.  Job j writes the (h,w) uint8 plane at out + out_offset (any byte
  * alignment; no byte outside the plane is written) from the uint8 HWC RGB photo of the same size at src + src_offset

@@ -167,6 +167,8 @@ SIGNATURES = {
     't2o_feather_weights': (_I, [_D, _P, _P]),
     't2o_feather_workspace_bytes': (_Z, [_P, _I]),
     't2o_feather_u8': (_I, [_P, _P, _P, _I, _P, _Z, _P]),
+    't2o_morph_workspace_bytes': (_Z, [_P, _I]),
+    't2o_morph_u8': (_I, [_P, _P, _P, _I, _P, _Z, _P]),
     't2o_select_u8': (_I, [_P, _P, _P, _I, _P]),
     't2o_refine_workspace_bytes': (_Z, [_P, _I]),
     't2o_refine_u8': (_I, [_P, _P, _P, _P, _I, _P, _Z, _P]),

@@ -23,6 +23,9 @@ functional.select_u8 launch writes the planes, functional.feather_u8's two launc
 ONE functional.replay_u8_any launch replays the list under them.  The new records carry 'select' and 'feather' along.
 A record that also has 'refine' (edit_cli --refine: {one of those names or 'all': [radius, eps]}) snaps each photo's planes
 to that photo's OWN luminance: functional.refine_u8's four launches run between the select launch and feather's two.
+A record that also has 'grow' (edit_cli --grow / --shrink / --border: {one of those names or 'all': [mode, radius]}) moves the
+boundary of each photo's planes by the same number of pixels at that photo's own size: functional.morph_u8's two launches
+run behind the select launch, in front of refine's and feather's.  The sequence is select, grow, refine, feather, fill.
 A record that has 'fill' (edit_cli --fill: the name of a plane) and 'select' under that name REMOVES what lies under that
 plane from every photo first: the plane is made per photo like the others (its own seed pixel, its own luminance, its own
 size), functional.fill_u8 fills the photos of a group in place in ONE call of three launches, and the list is then
@@ -108,6 +111,30 @@ def parse_refine(record):
                              info['select'])
 
 
+def parse_grow(record):
+    """The 'grow' of a record with 'select' -> {one of the selections' names or 'all': (mode, radius)}, {} when it has none.  A
+    record without 'select' is replayed globally, whatever else it holds.  Raises ValueError naming the entry: a value that
+    is not [mode, radius], an unknown mode, a radius that is no whole number in 0..64, a name that no selection goes by."""
+    from .edit_cli import parse_grow_args
+    info = record[0] if isinstance(record, list) and record else record
+    grow = info.get('grow') if isinstance(info, dict) else None
+    if not grow or not isinstance(info.get('select'), dict):
+        return {}                                                     # (painted planes stay with their photo, and so does what moved them)
+    if not isinstance(grow, dict):
+        raise ValueError('record: \'grow\' is {name: [mode, radius]}, got %r' % (grow,))
+    moves = {}
+    for name, value in grow.items():
+        if not (isinstance(name, str) and isinstance(value, (list, tuple)) and len(value) == 2 and value[0] in ('grow', 'shrink', 'border')
+                and isinstance(value[1], int) and not isinstance(value[1], bool)):
+            raise ValueError('record: \'grow\': entry %r: %r is not [\'grow\' | \'shrink\' | \'border\', a whole number of pixels]' % (name, value))
+        spec = [str(value[1]) if name == 'all' else '%s=%d' % (name, value[1])]
+        try:
+            moves.update(parse_grow_args(*[spec if value[0] == m else None for m in ('grow', 'shrink', 'border')], info['select']))
+        except ValueError as e:
+            raise ValueError('record: \'grow\': entry %r: %s' % (name, e))
+    return moves
+
+
 def parse_fill(record):
     """The 'fill' of a record -> None, or the name of the selection whose content is removed from every photo.  Raises
     ValueError naming the entry: a name whose plane is a painted mask (it stays with its photo), a name without a plane."""
@@ -127,13 +154,14 @@ def parse_fill(record):
                      % (fill, ', '.join(sorted(select)) if isinstance(select, dict) and select else 'none'))
 
 
-def local_planes(ops, select, feather, refine=None, fill=None):
+def local_planes(ops, select, feather, refine=None, fill=None, grow=None):
     """Which planes a photo needs for `ops` under parse_local's (select, feather) -> ([(terms in user units, sigma)],
     mask_of): the distinct planes, and per step the plane's number or -1.  A named entry wins over 'all', in select and in
     feather alike: an 'all' sigma stands for every plane that has none of its own (edit_cli.feather_argument).  With
     parse_refine's `refine` a plane is (terms, sigma, (radius, eps) or None), named entries winning in the same way.  With
     parse_fill's `fill` a third value follows: the number of that name's plane, which is made whether an operation uses it
-    or not and counts towards the 4."""
+    or not and counts towards the 4.  With parse_grow's `grow` every plane gains a last value, (mode, radius) or None, named
+    entries winning in the same way; growing or shrinking by 0 is None."""
     from .edit_cli import parse_select_terms
     planes, mask_of = [], []
 
@@ -142,6 +170,9 @@ def local_planes(ops, select, feather, refine=None, fill=None):
         if refine is not None:
             pair = refine.get(name, refine.get('all'))
             plane += (tuple(pair) if pair is not None and pair[0] > 0 else None,)
+        if grow is not None:
+            move = grow.get(name, grow.get('all'))
+            plane += (tuple(move) if move is not None and (move[1] > 0 or move[0] == 'border') else None,)
         if plane not in planes:
             planes.append(plane)
         return planes.index(plane)
@@ -156,7 +187,7 @@ def local_planes(ops, select, feather, refine=None, fill=None):
     return (planes, mask_of) if fill is None else (planes, mask_of, fill_no)
 
 
-def apply_record_local(images, ops, params, select, feather, multi_img=False, device=None, refine=None, fill=None):
+def apply_record_local(images, ops, params, select, feather, multi_img=False, device=None, refine=None, fill=None, grow=None):
     """apply_record under the selections of parse_local: the same result layout.  One upload; per group of photos that
     together name at most 4 planes: one select_u8 launch, refine_u8's four where parse_refine's `refine` gives a radius,
     feather_u8 where a sigma is given, one replay launch.  A 'wand' / 'wand8' term is resolved per photo at that photo's
@@ -164,11 +195,18 @@ def apply_record_local(images, ops, params, select, feather, multi_img=False, de
     connectivity) of the photo, in calls of at most 4 in front of the group's select launch; the region planes lie in room
     reserved on the device behind the uploaded buffer (no byte is uploaded for it), where the select launch reads them as
     'plane' terms.  With parse_fill's `fill` the photos of a group are filled in place under their own plane of that name by
-    one functional.fill_u8 call, behind feather and in front of the replay."""
+    one functional.fill_u8 call, behind feather and in front of the replay.  With parse_grow's `grow` one functional.morph_u8
+    call per group moves the planes' boundaries in place, behind the select launch and in front of refine."""
     from . import functional as T
     from .edit import refine_eps2, select_terms, upload_with_room, wand_keys, wand_resolved
     assert (MAX_STEPS, MAX_JOBS, PARAM_PAD, MAX_PLANES) == (T.REPLAY_MAX_STEPS, T.REPLAY_MAX_JOBS, T.PARAM_PAD, T.REPLAY_MAX_MASKS)
-    planes, mask_of, *fill_no = local_planes(ops, select, feather, refine or None, fill)
+    if grow:
+        planes, mask_of, *fill_no = local_planes(ops, select, feather, refine or {}, fill, grow)
+        moves = [p[3] for p in planes]
+        planes = [p[:3] for p in planes]
+    else:
+        planes, mask_of, *fill_no = local_planes(ops, select, feather, refine or None, fill)
+        moves = [None] * len(planes)
     snaps = [(p[2][0], refine_eps2(p[2][1])) if len(p) == 3 and p[2] else None for p in planes]      # before any device use
     planes = [p[:2] for p in planes]
     if not planes:                                                    # no operation of the list is selected for
@@ -197,12 +235,14 @@ def apply_record_local(images, ops, params, select, feather, multi_img=False, de
     per = MAX_PLANES // len(planes)                                   # photos of a group
     for a in range(0, len(images), per):
         group = list(range(a, min(a + per, len(images))))
-        sel_jobs, snap_jobs, soft_jobs, jobs, where, at, pos = [], [], [], [], {}, 0, 0
+        sel_jobs, move_jobs, snap_jobs, soft_jobs, jobs, where, at, pos = [], [], [], [], [], {}, 0, 0
         for i in group:
             h, w = shapes[i]
             for k, (_, sigma) in enumerate(planes):
                 where[i, k] = len(sel_jobs)
                 sel_jobs.append((offsets[i], at, h, w, rules[i][k]))
+                if moves[k]:
+                    move_jobs.append((at, at, h, w, moves[k][1], moves[k][0]))
                 if snaps[k]:
                     snap_jobs.append((offsets[i], at, at, h, w) + snaps[k])
                 if sigma > 0.0:
@@ -215,6 +255,8 @@ def apply_record_local(images, ops, params, select, feather, multi_img=False, de
         for k in range(0, len(wand_jobs), T.REGION_MAX_JOBS):
             T.region_u8(dev_buffer, wand_jobs[k:k + T.REGION_MAX_JOBS], out=dev_buffer)
         plane_buffer = T.select_u8(dev_buffer, sel_jobs)
+        if move_jobs:                                                 # at most 4 planes to a group: one call
+            T.morph_u8(plane_buffer, move_jobs)
         if snap_jobs:
             T.refine_u8(dev_buffer, plane_buffer, snap_jobs)
         if soft_jobs:
@@ -290,16 +332,19 @@ def main(argv=None):
     local = parse_local(record)
     refine = parse_refine(record)
     fill = parse_fill(record)
+    grow = parse_grow(record)
     images = [decode_image(p) for p in args.img]
     from .edit_cli import write_outputs
     infos = []
     if local is None:
         results, carried = apply_record(images, ops, params, args.multi_img), {}
     else:
-        results = apply_record_local(images, ops, params, local[0], local[1], args.multi_img, refine=refine, fill=fill)
+        results = apply_record_local(images, ops, params, local[0], local[1], args.multi_img, refine=refine, fill=fill, **({'grow': grow} if grow else {}))
         carried = {'select': local[0], 'feather': local[1] or None, 'fill': fill}
         if refine:
             carried['refine'] = refine
+        if grow:
+            carried['grow'] = grow
     for path, img, steps in zip(args.img, images, results):
         info = write_outputs(args.save_dir, path, request, img, steps, ops, params, args.multi_img, **carried)
         info['record'] = args.record

@@ -127,6 +127,47 @@ def checked_refine(refine, masks):
     return {plane: pair for plane, pair in by_plane.items() if pair[0] > 0}
 
 
+def _grow_value(key, value):
+    """A boundary move as given -- a whole number of pixels (positive grows, negative shrinks) or (mode, radius) with mode one
+    of functional.MORPH_MODES -- -> (mode, radius >= 0)."""
+    if isinstance(value, (tuple, list)):
+        if not (len(value) == 2 and isinstance(value[0], str) and value[0] in T.MORPH_MODES):
+            raise ValueError('edit_image: grow %r = %r is neither a number of pixels nor (%s, radius)' % (key, value, ' | '.join(repr(m) for m in T.MORPH_MODES)))
+        mode, radius = value
+        signed = False
+    else:
+        mode, radius, signed = None, value, True
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or radius != radius or radius != int(radius):
+        raise ValueError('edit_image: grow %r = %r, a radius is a whole number of pixels' % (key, value))
+    radius = int(radius)
+    if not (-T.MORPH_MAX_RADIUS if signed else 0) <= radius <= T.MORPH_MAX_RADIUS:
+        raise ValueError('edit_image: grow %r = %r, a radius lies in %s..%d' % (key, value, '-%d' % T.MORPH_MAX_RADIUS if signed else '0', T.MORPH_MAX_RADIUS))
+    return (mode, radius) if mode is not None else ('shrink', -radius) if radius < 0 else ('grow', radius)
+
+
+def checked_grow(grow, masks):
+    """grow (None, a whole number of pixels in -64..64 -- positive grows, negative shrinks --, ('border', R), or {key of masks:
+    either}) -> {id of the mask object: (mode, radius)} for functional.morph_u8.  Two keys that name one plane must agree;
+    growing or shrinking by 0 leaves its plane exactly as it is (it is not binarised); a border of 0 is the empty plane."""
+    if grow is None:
+        return {}
+    if masks is None:
+        raise ValueError('edit_image: grow without masks -- there is no plane to grow')
+    if not isinstance(grow, dict):
+        grow = {key: grow for key in masks}
+    by_plane = {}
+    for key, value in grow.items():
+        if key not in masks:
+            raise ValueError('edit_image: grow key %r names no mask (masks: %s)' % (key, ', '.join(repr(k) for k in masks)))
+        pair = _grow_value(key, value)
+        if pair[1] == 0 and pair[0] != 'border':
+            pair = ('grow', 0)                                       # growing and shrinking by nothing agree
+        if by_plane.setdefault(id(masks[key]), pair) != pair:
+            raise ValueError('edit_image: grow %r = %r, but another key moves the same plane by %r'
+                             % (key, pair, by_plane[id(masks[key])]))
+    return {plane: pair for plane, pair in by_plane.items() if pair[1] > 0 or pair[0] == 'border'}
+
+
 def _round_unit(v, scale):
     """floor(v * scale + 0.5) in double: the host rounding of a selection's user units."""
     return int(np.floor(np.float64(v) * np.float64(scale) + 0.5))
@@ -260,7 +301,7 @@ def _key_targets(key, what):
     raise ValueError('edit_image: %s key %r is neither \'all\' nor an executor operator index 0..7' % (what, key))
 
 
-def select_plan(select, masks, feather, h, w, refine=None, keys=None):
+def select_plan(select, masks, feather, h, w, refine=None, keys=None, grow=None):
     """The planes of an edit_image call that gives `select` -- checked without any device use.  select: {executor operator
     index or 'all': selection in user units}, keyed like masks.  Every key of select or masks gets a plane: its selection,
     multiplied by its painted mask when the SAME key has one (a 'plane' term: the intersection); a key with only a painted
@@ -268,7 +309,8 @@ def select_plan(select, masks, feather, h, w, refine=None, keys=None):
     sigma_of): the distinct painted planes to upload, per plane (integer terms, number of its painted plane or None),
     {operator index: plane number} ('all' first, an entry for one operator wins), {plane number: sigma > 0}.  With `refine`
     (keyed like feather; checked_refine) a fifth value follows: {plane number: (radius > 0, E)}.  keys: a dict that receives
-    {key of select or masks: plane number}."""
+    {key of select or masks: plane number}.  With `grow` (keyed like feather; checked_grow) one more value follows behind
+    those: {plane number: (mode, radius)}."""
     if not isinstance(select, dict) or not select:
         raise ValueError('edit_image: select is {executor operator index or \'all\': [terms]}')
     masks = masks or {}
@@ -301,10 +343,14 @@ def select_plan(select, masks, feather, h, w, refine=None, keys=None):
     handles = [object() for _ in specs]                               # checked_feather tells planes apart by identity
     by_handle = checked_feather(feather, {key: handles[no] for key, no in tokens.items()})
     sigma_of = {no: by_handle[id(hd)] for no, hd in enumerate(handles) if id(hd) in by_handle}
-    if refine is None:
-        return painted, specs, by_op, sigma_of
-    by_handle = checked_refine(refine, {key: handles[no] for key, no in tokens.items()})
-    return painted, specs, by_op, sigma_of, {no: by_handle[id(hd)] for no, hd in enumerate(handles) if id(hd) in by_handle}
+    plan = (painted, specs, by_op, sigma_of)
+    if refine is not None:
+        by_handle = checked_refine(refine, {key: handles[no] for key, no in tokens.items()})
+        plan += ({no: by_handle[id(hd)] for no, hd in enumerate(handles) if id(hd) in by_handle},)
+    if grow is not None:
+        by_handle = checked_grow(grow, {key: handles[no] for key, no in tokens.items()})
+        plan += ({no: by_handle[id(hd)] for no, hd in enumerate(handles) if id(hd) in by_handle},)
+    return plan
 
 
 def _append_planes(buffer, planes):
@@ -341,7 +387,7 @@ def checked_fill(fill, masks, select):
     return fill
 
 
-def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, select=None, refine=None, fill=None):
+def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, select=None, refine=None, fill=None, grow=None):
     """img_u8_hwc: the decoded photo, uint8 (h,w,3) RGB (array or CPU tensor); x: (1, L) request token ids.
     Returns (steps_u8, ops, params):
       steps_u8  (max(n,1), h, w, 3) uint8 GPU tensor: picture k is the photo after the first k+1 of the n chosen operators,
@@ -377,7 +423,7 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, 
     and every loop follows strictly falling indices: include/t2onet_hip.h); their hard 0 / 255 planes are written into room
     reserved ON THE DEVICE behind the photo and the painted planes -- no byte is uploaded for it -- and the select launch
     reads each as a 'plane' term with the term's invert flag.  refine and feather soften them like any plane.  The order of
-    the stages is region, select, refine, feather, proxy, replay.  Without a wand term the call issues exactly the launches
+    the stages is region, select, grow, refine, feather, proxy, replay.  Without a wand term the call issues exactly the launches
     and the one upload it issued before there was one.
     refine: None, a radius in pixels of the photo (every plane), (radius, eps), or {key of masks / select: either} -- the
     planes are snapped to the photo's own edges by functional.refine_u8's exact integer guided filter (guide = the photo's
@@ -387,28 +433,39 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, 
     share one plane must agree; refine without masks or select is an error; None is the path without it, launch for launch.
     fill: None, or a key that masks or select also carries -- the natural one is 4, the inpaint slot; any operator index or
     'all' is allowed, and the plane then also localises those operators as it does without fill.  What lies under that
-    plane is REMOVED from the photo: the plane is made exactly as above (region, select, refine, feather), then
+    plane is REMOVED from the photo: the plane is made exactly as above (region, select, grow, refine, feather), then
     functional.fill_u8 (three launches) replaces every pixel whose plane byte M is > 0, blended by M / 255, with the exact
     integer push-pull fill of include/t2onet_hip.h from the pixels with M = 0 -- IN PLACE in the device buffer, before the proxy
     is made.  The actor therefore decides on the filled picture, the replay edits the filled picture, and every picture of
-    steps_u8 carries the fill.  The order of the stages is region, select, refine, feather, fill, proxy, replay: wand seeds
+    steps_u8 carries the fill.  The order of the stages is region, select, grow, refine, feather, fill, proxy, replay: wand seeds
     and select rules read the ORIGINAL bytes.  A soft plane has M > 0 in its soft band, so refine and feather also keep the
     object's anti-aliased rim out of the fill's sources.  The fill plane counts towards the four planes of a call.  It is a
     SMOOTH fill -- sky, walls, blurred backgrounds; it synthesises no texture and is not the reference's inpaint_obj network,
     which stays unexecutable here (operators.InpaintOperator).  A fill key without a plane is a ValueError before any device
-    use; None is the path without it, launch for launch and upload for upload."""
+    use; None is the path without it, launch for launch and upload for upload.
+    grow: None, a whole number of pixels of the photo in -64..64 (every plane; positive GROWS the selection, negative SHRINKS
+    it), ('border', R) -- the band of R pixels either side of the selection's edge --, or {key of masks / select: either}.  The
+    plane is binarised at 128 and its boundary moved by the EXACT Euclidean distance (functional.morph_u8, two launches,
+    whatever the number of planes; the definition is in include/t2onet_hip.h; the frame edge is no edge of the selection) IN
+    PLACE in the buffer the later stages read.  The order of the stages is region, select, grow, refine, feather, fill, proxy,
+    replay: a wand region grown by a few pixels takes the object's anti-aliased rim, its halo and its contact shadow out of
+    the fill's sources, and refine and feather then soften the hard 0 / 255 plane that grow leaves.  Keys that share one plane
+    must agree; 0 leaves a plane exactly as it is; grow without masks or select is an error; None is the path without it,
+    launch for launch and upload for upload."""
     img = T._u8_hwc(img_u8_hwc)
     h, w = img.shape[:2]
     plane_of = {}
-    plan = select_plan(select, masks, feather, h, w, refine if refine is not None else {}, plane_of) if select is not None else None    # before any device use
+    plan = (select_plan(select, masks, feather, h, w, refine if refine is not None else {}, plane_of, grow if grow is not None else {})
+            if select is not None else None)                                                 # before any device use
     sigma_of = checked_feather(feather, masks) if plan is None else {}                       # before any device use
     refine_of = checked_refine(refine, masks) if plan is None else {}                        # before any device use
+    grow_of = checked_grow(grow, masks) if plan is None else {}                              # before any device use
     fill = checked_fill(fill, masks, select)                                                 # before any device use
     dev = next(model.parameters()).device
     opt = model.opt
     slot_of = {}
     if plan is not None:
-        planes, specs, by_op, plane_sigma, plane_refine = plan
+        planes, specs, by_op, plane_sigma, plane_refine, plane_grow = plan
     else:
         planes, by_op = _checked_masks(masks, h, w, slot_of) if masks is not None else ([], {})
     local = masks is not None or plan is not None
@@ -433,11 +490,15 @@ def edit_image(model, img_u8_hwc, x, proxy_short=600, masks=None, feather=None, 
                 for k, (terms, slot) in enumerate(specs)]
         mask_buffer = T.select_u8(dev_buffer, jobs)
         mask_offsets = [k * h * w for k in range(len(specs))]
+        if plane_grow:
+            T.morph_u8(mask_buffer, [(mask_offsets[k],) * 2 + (h, w, r, mode) for k, (mode, r) in plane_grow.items()])
         if plane_refine:
             T.refine_u8(dev_buffer, mask_buffer, [(int(descs[0]['offset']),) + (mask_offsets[k],) * 2 + (h, w, r, E) for k, (r, E) in plane_refine.items()])
         if plane_sigma:
             T.feather_u8(mask_buffer, [(mask_offsets[k],) * 2 + (h, w, sigma) for k, sigma in plane_sigma.items()])
     else:
+        if grow_of:
+            T.morph_u8(dev_buffer, [(mask_offsets[slot_of[p]],) * 2 + (h, w, r, mode) for p, (mode, r) in grow_of.items()])
         if refine_of:
             T.refine_u8(dev_buffer, dev_buffer, [(int(descs[0]['offset']),) + (mask_offsets[slot_of[p]],) * 2 + (h, w, r, E) for p, (r, E) in refine_of.items()])
         if sigma_of:

@@ -32,14 +32,22 @@ RADIUS pixels (a whole number, at most 64); EPS, a fraction of full scale in (0,
 counts as an edge.  NAME is a name a --mask or --select was given under; without a name every plane is refined.  The
 record then also holds 'refine': {name or 'all': [radius, eps]}, which apply_cli replays under each photo's own luminance.
 
+--grow [NAME=]R, --shrink [NAME=]R and --border [NAME=]R (each repeatable) move a plane's boundary by R pixels of the photo (a
+whole number in 0..64) on the device, by the exact Euclidean distance (edit.edit_image's `grow`, functional.morph_u8): the
+plane is binarised at 128 and grown, shrunk, or turned into the band of R pixels either side of its edge -- after --select,
+before --refine and --feather, which soften the hard plane again.  NAME is a name a --mask or --select was given under;
+without a name every plane is moved (a named flag wins); two of these flags on one plane are an error.  The frame edge is no
+edge of the selection.  The record then also holds 'grow': {name or 'all': [mode, radius]}, which apply_cli carries to other
+photos by the same number of pixels.
+
 --fill [NAME] REMOVES what lies under a plane before anything else is decided: NAME is an operator name a --mask or
 --select was given under (default: inpaint, the slot of the operator this project cannot execute).  The plane is made as
-above (wand, rule, painted mask, --refine, --feather); then the pixels under it are replaced on the device, blended by the
+above (wand, rule, painted mask, --grow, --refine, --feather); then the pixels under it are replaced on the device, blended by the
 plane's byte, with an exact integer push-pull fill from the pixels the plane leaves at 0 (edit.edit_image's `fill`,
 functional.fill_u8).  The actor decides on the filled photo and every written picture carries the fill.  It is a SMOOTH
 fill: it suits sky, walls and blurred backgrounds, synthesises no texture and is not the reference's inpaint network.  The
 record then also holds 'fill': NAME, which apply_cli carries to other photos when the plane is a --select.  For example
-    --select 'inpaint=wand:0.5,0.4:0.1' --refine inpaint=6 --feather inpaint=2 --fill
+    --select 'inpaint=wand:0.5,0.4:0.1' --grow inpaint=4 --feather inpaint=2 --fill
 
 The actor decides on a proxy of the photo (short side --proxy_short, the test loader's 600; a smaller photo is its own
 proxy) and the decision is applied to the photo at its native size by the fused 8-bit replay kernel (edit.edit_image).
@@ -143,6 +151,44 @@ def parse_refine_args(specs, named):
             raise ValueError('--refine %s: EPS must lie in (0, 1]' % spec)
         refines[name] = (radius, eps)
     return refines
+
+
+def parse_grow_args(grows, shrinks, borders, named):
+    """--grow, --shrink and --border values ([NAME=]R each) -> {name or 'all': (mode, radius)}; named: every name a plane goes
+    by.  NAME must be one of them, R a whole number in 0..64; no NAME means every plane.  Two flags on one plane are an
+    error.  Raises ValueError naming the flag."""
+    moves = {}
+    for mode, specs in (('grow', grows), ('shrink', shrinks), ('border', borders)):
+        for spec in specs or []:
+            head, sep, tail = spec.partition('=')
+            name, text = (head, tail) if sep else ('all', spec)
+            if not named:
+                raise ValueError('--%s %s: there is no --mask or --select to %s' % (mode, spec, mode))
+            if sep and name not in named:
+                raise ValueError('--%s %s: no --mask or --select was given under %r (given: %s)' % (mode, spec, name, ', '.join(sorted(named))))
+            try:
+                radius = int(text)
+            except ValueError:
+                raise ValueError('--%s %s: R %r is not a whole number' % (mode, spec, text))
+            if not 0 <= radius <= 64:
+                raise ValueError('--%s %s: R must lie in 0..64' % (mode, spec))
+            if name in moves:
+                raise ValueError('--%s %s: %s already has --%s %d; one of --grow, --shrink and --border to a plane'
+                                 % (mode, spec, 'every plane' if name == 'all' else 'the plane %r' % name, moves[name][0], moves[name][1]))
+            moves[name] = (mode, radius)
+    return moves
+
+
+def grow_argument(moves, named):
+    """{name or 'all': (mode, radius)} of parse_grow_args -> the `grow` argument of edit.edit_image, keyed like the planes of
+    `named`.  An unnamed value stands for every plane; a named one wins over it (as feather_argument)."""
+    if not moves:
+        return None
+    grow = {}
+    for name in named:
+        if name in moves or 'all' in moves:
+            grow['all' if name == 'all' else ACTIONS.index(name)] = tuple(moves.get(name, moves.get('all')))
+    return grow
 
 
 def parse_fill_arg(name, named):
@@ -251,10 +297,10 @@ def load_masks(named, h, w):
 
 
 def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, multi_img=False, masks=None, feather=None, select=None,
-                  refine=None, fill=None):
+                  refine=None, fill=None, grow=None):
     """The files of one edit (see the module docstring); steps_u8: (max(n,1), h, w, 3) uint8 array; masks: {name: file}
     of a local edit, feather: {name: sigma}, select: {name: terms as given}, refine: {name: (radius, eps)} and fill: the
-    name of the plane whose content was removed, each recorded when given.  Returns the record."""
+    name of the plane whose content was removed, grow: {name: (mode, radius)}, each recorded when given.  Returns the record."""
     from PIL import Image
     name, ext = os.path.splitext(os.path.basename(img_path))
     out_dir = os.path.join(save_dir, name)
@@ -276,6 +322,8 @@ def write_outputs(save_dir, img_path, request, img_u8, steps_u8, ops, params, mu
         info['refine'] = {name: [int(v[0]), float(v[1])] for name, v in refine.items()}
     if fill:
         info['fill'] = str(fill)
+    if grow:
+        info['grow'] = {name: [str(v[0]), int(v[1])] for name, v in grow.items()}
     with open(os.path.join(out_dir, name + '.json'), 'w') as f:
         json.dump([info], f)
     return info
@@ -306,6 +354,11 @@ def main(argv=None):
                     help='snap a plane to the photo\'s own edges on the device (guided filter, window RADIUS <= 64 pixels, EPS in '
                          '(0, 1], default 0.02) before it is feathered and used; NAME = a name a --mask or --select was given '
                          'under, without it every plane; repeatable')
+    for flag, what in (('grow', 'grow a plane'), ('shrink', 'shrink a plane'), ('border', 'turn a plane into the band of R pixels either side of its edge')):
+        ap.add_argument('--' + flag, action='append', default=None, metavar='[NAME=]R',
+                        help='%s by R pixels (a whole number, at most 64; exact Euclidean distance) on the device, after --select and '
+                             'before --refine and --feather; NAME = a name a --mask or --select was given under, without it every '
+                             'plane; repeatable, one of --grow, --shrink and --border to a plane' % what)
     ap.add_argument('--fill', nargs='?', const='inpaint', default=None, metavar='NAME',
                     help='remove what lies under a plane before the edit: the pixels under the plane a --mask or --select was given '
                          'under NAME (default inpaint) are replaced on the device by a smooth push-pull fill from the pixels around '
@@ -316,18 +369,21 @@ def main(argv=None):
     planes = dict(named, **rules)                                                  # every name a plane goes by
     sigmas = parse_feather_args(args.feather, planes)                              # before the model: a wrong value fails early
     refines = parse_refine_args(args.refine, planes)
+    moves = parse_grow_args(args.grow, args.shrink, args.border, planes)
     fill_name = parse_fill_arg(args.fill, planes)
     img = decode_image(args.img)
     masks = load_masks(named, img.shape[0], img.shape[1]) if named else None       # before the model: a wrong mask fails early
     feather = feather_argument(sigmas, planes)
     select = select_argument(rules)
     refine = refine_argument(refines, planes)
+    grow = grow_argument(moves, planes)
     fill = None if fill_name is None else 'all' if fill_name == 'all' else ACTIONS.index(fill_name)
     if select:
         from .edit import select_plan
-        select_plan(select, masks, feather, img.shape[0], img.shape[1], refine)    # a gradient that collapses on this photo, too many planes
+        select_plan(select, masks, feather, img.shape[0], img.shape[1], refine, grow=grow)      # a gradient that collapses on this photo, too many planes
     else:
-        from .edit import checked_feather, checked_refine
+        from .edit import checked_feather, checked_grow, checked_refine
+        checked_grow(grow, masks)
         checked_feather(feather, masks)                                            # two names, one file, two sigmas
         checked_refine(refine, masks)
 
@@ -341,9 +397,9 @@ def main(argv=None):
     model.load_state_dict(torch.load(args.checkpoint, map_location='cpu'), strict=False)      # as the demo (:129)
     model.to(device)
     steps_u8, ops, params = edit_image(model, img, request_to_idx(args.request, vocab2id, opt), args.proxy_short, masks=masks,
-                                      feather=feather, select=select, **dict({'refine': refine} if refine else {}, **({'fill': fill} if fill is not None else {})))
+                                      feather=feather, select=select, **dict({'refine': refine} if refine else {}, **dict({'fill': fill} if fill is not None else {}, **({'grow': grow} if grow else {}))))
     info = write_outputs(args.save_dir, args.img, args.request, img, steps_u8.cpu().numpy(), ops, params.cpu(), args.multi_img,
-                         masks=named or None, feather=sigmas or None, select=rules or None, refine=refines or None, fill=fill_name)
+                         masks=named or None, feather=sigmas or None, select=rules or None, refine=refines or None, fill=fill_name, grow=moves or None)
     print('%s: %s -> %s' % (args.request, ', '.join(n for n, _ in info['operations']) or '(no operator)',
                             os.path.join(args.save_dir, os.path.splitext(os.path.basename(args.img))[0], info['output'])))
     return info

@@ -2387,6 +2387,75 @@ def feather_u8(buffer, jobs, out=None):
     return out
 
 
+# ---- mask morphology (t2o_morph.hip): a plane's boundary moved by an exact Euclidean distance in pixels ----
+
+MORPH_MAX_JOBS, MORPH_MAX_RADIUS = 4, 64
+MORPH_MODES = ('grow', 'shrink', 'border')                   # T2O_MORPH_GROW .. T2O_MORPH_BORDER
+
+
+class MorphJob(ctypes.Structure):
+    """t2o_morph_job_t of include/t2onet_hip.h (field for field)."""
+    _fields_ = [('src_offset', ctypes.c_longlong), ('out_offset', ctypes.c_longlong), ('h', ctypes.c_int), ('w', ctypes.c_int),
+                ('radius', ctypes.c_int), ('mode', ctypes.c_int)]
+
+
+def morph_jobs(jobs):
+    """jobs: a sequence of (src_offset, out_offset, h, w, radius, mode) -> the ctypes array t2o_morph_u8 takes.  mode: one of
+    MORPH_MODES or its index; any other integer goes to the library as it is (it refuses it)."""
+    arr = (MorphJob * max(len(jobs), 1))()
+    for c, (src_offset, out_offset, h, w, radius, mode) in zip(arr, jobs):
+        if isinstance(mode, str):
+            if mode not in MORPH_MODES:
+                raise ValueError('morph_u8: mode %r is none of %s' % (mode, ', '.join(MORPH_MODES)))
+            mode = MORPH_MODES.index(mode)
+        c.src_offset, c.out_offset, c.h, c.w, c.radius, c.mode = int(src_offset), int(out_offset), int(h), int(w), int(radius), int(mode)
+    return arr
+
+
+_morph_ws = {}
+
+
+def _morph_workspace(need, device):
+    """The distance fields of morph_u8: cached per device and stream like _feather_workspace, a buffer of its own -- a
+    24 Mpx plane needs 24 MB (48 MB for a border), which the shared scratch should not be grown to."""
+    return _scratch(need, device, _morph_ws, 8)
+
+
+def morph_u8(buffer, jobs, out=None):
+    """Grow, shrink or border uint8 planes on the device in TWO launches, whatever their number (t2o_morph_u8): job j =
+    (src_offset, out_offset, h, w, radius, mode) reads the (h, w) plane at byte src_offset of the 1-D uint8 GPU tensor
+    `buffer` (any alignment), takes S = the bytes >= 128, and writes the hard 0 / 255 plane of mode 'grow' (within `radius`
+    pixels of S, exact Euclidean distance), 'shrink' (in S and further than radius from every pixel of the frame outside S)
+    or 'border' (grown and not shrunk) at byte out_offset of `out` -- of `buffer` itself when out is None: in place where
+    the two offsets agree.  radius: a whole number in 0..64.  The frame edge is no edge of the selection.  At most 4 jobs;
+    their destinations may not overlap each other, a source may overlap any destination.  Returns out."""
+    if not (torch.is_tensor(buffer) and buffer.is_cuda and buffer.dtype == torch.uint8 and buffer.is_contiguous()):
+        raise ValueError('morph_u8: buffer must be a contiguous uint8 GPU tensor')
+    if out is None:
+        out = buffer
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == buffer.device):
+        raise ValueError('morph_u8: out must be a contiguous uint8 GPU tensor on the buffer\'s device')
+    jobs = [tuple(j) for j in jobs]
+    if not 1 <= len(jobs) <= MORPH_MAX_JOBS:
+        raise ValueError('morph_u8: 1 to 4 jobs per call, got %d' % len(jobs))
+    for j, (so, oo, h, w, radius, mode) in enumerate(jobs):
+        if radius != int(radius):
+            raise ValueError('morph_u8: job %d: the radius %r is not a whole number' % (j, radius))
+        if not (h > 0 and w > 0):
+            continue                                             # the library refuses it
+        if not (0 <= so and so + h * w <= buffer.numel()):
+            raise ValueError('morph_u8: job %d reads outside the %d-byte buffer' % (j, buffer.numel()))
+        if not (0 <= oo and oo + h * w <= out.numel()):
+            raise ValueError('morph_u8: job %d writes outside the %d-byte output' % (j, out.numel()))
+    lib = _lib.load()
+    table = morph_jobs(jobs)
+    need = lib.t2o_morph_workspace_bytes(table, len(jobs))       # 0 for a table the library refuses: it says why below
+    ws = _morph_workspace(need, buffer.device)
+    rc = lib.t2o_morph_u8(_ptr(buffer), _ptr(out), table, len(jobs), _ptr(ws), ws.numel(), _stream(buffer.device))
+    replay_status(rc, 't2o_morph_u8')
+    return out
+
+
 # ---- selections (t2o_select.hip): the mask planes of a local edit computed from a rule, where the photo already lies ----
 
 SELECT_MAX_JOBS, SELECT_MAX_TERMS = 4, 4
